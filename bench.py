@@ -15,8 +15,16 @@ Each rank is a colocated worker + server shard (one process per GPU):
 Weak scaling: the per-GPU batch is fixed, the global batch is N*B.
 
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+                        [--dump-outputs DIR] [--full]
         (N > 1 via: python -m torch.distributed.run --nproc-per-node N
          --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints one JSON line.
+--dump-outputs DIR also writes what the last timed step computed (see
+``dump_outputs``).  --full is for measurements beyond the headline figure
+that take runs of their own; the benchmark has none today (the N > 1
+calibration windows choose the configuration the headline runs, so they stay
+in a plain run), and the option changes nothing yet.
 """
 from __future__ import annotations
 
@@ -33,6 +41,45 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 METRIC = "training samples/sec (whole node), 1B-feature sparse LR at 1/2/4/8 MI355X"
 BASELINE_SAMPLES_PER_SEC = None  # reference publishes no number
+DUMP_KEYS = 1 << 20  # keys of the last timed batch whose trained rows --dump-outputs writes
+
+
+def dump_outputs(out_dir, worker, loss_sum, rank, world):
+    """--dump-outputs: what the last timed step computed, as ``<name>.npy``
+    (rank 0 writes; a collective at N > 1, every rank calls it):
+
+      loss_sum.npy     float64 [1]: the sum over the sharded loss accumulator
+                       ``step()`` returned (which shard a workgroup adds into
+                       is not fixed, the sum is what a caller reads)
+      weight_keys.npy  float64 [m]: a fixed, seeded sample of this rank's keys
+                       of the last timed batch (keys < 2^53: exact)
+      weights.npy      float32 [m, 1]: the table's rows of those keys after the
+                       step's push, read through the engine's read-only lookup
+
+    12 MB at the default shape.  The batch of a step is a function of the
+    generator's seed and the step index, and a new key's row of its key, so
+    the same arguments give the same inputs in every run."""
+    import numpy as np
+
+    eng, d = worker.engine, worker.data
+    dev = eng.device
+    last = worker.step_idx - 1
+    torch.cuda.synchronize(dev)  # the route stream may still be producing
+    keys = torch.empty(d.batch_size * d.num_fields, dtype=torch.int64, device=dev)
+    labels = torch.empty(d.batch_size, dtype=torch.float32, device=dev)
+    d.generate(last, rank, world, keys, labels)
+    n = keys.numel()
+    if n > DUMP_KEYS:
+        pos = np.sort(np.random.default_rng(d.seed).choice(n, DUMP_KEYS, replace=False))
+        keys = keys[torch.from_numpy(pos).to(dev)]
+    rows = eng.lookup(keys)
+    loss = np.array([float(loss_sum.double().sum().item())], dtype=np.float64)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "loss_sum.npy"), loss)
+        np.save(os.path.join(out_dir, "weight_keys.npy"), keys.cpu().numpy().astype(np.float64))
+        np.save(os.path.join(out_dir, "weights.npy"),
+                rows.float().cpu().numpy().reshape(keys.numel(), -1))
 
 
 def main(argv=None):
@@ -78,6 +125,11 @@ def main(argv=None):
                          "every window")
     ap.add_argument("--cal-windows", type=int, default=2,
                     help="N>1: alternating (synchronous, pulled-ahead) calibration windows")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (its loss and "
+                         "the trained rows of a seeded sample of its keys) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure (none today)")
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args(argv)
 
@@ -284,6 +336,9 @@ def main(argv=None):
         torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs:
+        # step() returns the worker's loss accumulator, the same tensor every step
+        dump_outputs(a.dump_outputs, worker, worker.loss_sum, rank, world)
 
     t = torch.tensor([elapsed], dtype=torch.float64)
     t_min = t.clone()

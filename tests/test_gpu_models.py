@@ -564,7 +564,20 @@ def _record_exchange_body(dev, occ):
     assert tr.keys() == tu.keys()
     ks = list(tu.keys())
     a, b = np.stack([tu[k] for k in ks]), np.stack([tr[k] for k in ks])
-    np.testing.assert_allclose(b, a, rtol=1e-3, atol=1e-5)
+    # rows [w, h]: rtol 1e-3, atol 1e-5 — and, for w, the conditioning of the
+    # AdaGrad step lr * g / sqrt(h + eps): its slope in g is lr / sqrt(h + eps),
+    # so where a key's occurrences' gradients cancel (g^2 ~ h below eps = 1e-8:
+    # one such key in this data, h = 1.6e-9) the last bits of g decide w.  g is
+    # a sum of a few terms of magnitude < 1, each known to an ulp: 8 * 2^-24
+    # bounds its error (two runs of the SAME exchange differed by 1-2 * 2^-24
+    # there, 4.7e-5 / 9.5e-5 in w, and by one ulp of w, 6e-8, in every other
+    # row); for a row with h >= 1 the term adds < 5e-8
+    lr, eps = 0.1, 1e-8  # _graph_worker's optimizer
+    tol = 1e-5 + 1e-3 * np.abs(a)
+    tol[:, 0] += lr * 8 * 2.0 ** -24 / np.sqrt(np.minimum(a[:, 1], b[:, 1]) + eps)
+    assert np.isfinite(a).all() and np.isfinite(b).all() and (a[:, 1] >= 0).all()
+    bad = np.abs(b - a) > tol
+    assert not bad.any(), (int(bad.sum()), a[bad.any(1)][:5], b[bad.any(1)][:5])
 
 
 def test_lr_slot32_matches_slot64(dev, monkeypatch):
@@ -865,6 +878,48 @@ def test_bench_graph_mode_times_whole_periods():
     assert g["config"]["hipgraph"] is True and e["config"]["hipgraph"] is False
     assert g["steps"] == 16 and g["ms_per_step"] > 0
     assert g["config"]["loss_last"] == pytest.approx(e["config"]["loss_last"], rel=1e-4, abs=1e-5)
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """bench.py --dump-outputs: the last timed step's loss and the trained
+    rows of its keys as .npy files (float32 / float64), the same keys from run
+    to run (seeded inputs) and the same rows and loss up to the order of the
+    fp32 sums (duplicate merge, loss shards).
+
+    Row tolerance: a key's gradient g = sum (p_i - y_i) is known to a few
+    ulp of 1 (the order of the sum, and p through the ulp-level differences
+    of the 39 weights under it: 8 * 2^-24 bounds it with room).  AdaGrad
+    steps by lr * g / sqrt(h + eps), h >= g^2, whose slope in g is at most
+    lr / sqrt(eps) — reached by a key whose occurrences' gradients cancel
+    (labels 0 and 1 at p ~ 0.5) — so two correct runs may differ by
+    lr / sqrt(eps) * 8 * 2^-24 = 2.4e-4 in such a row.  A wrong row (another
+    key's, a lost update) is off by the step size lr = 0.05, 200 times that."""
+    base = ["--batch", "4096", "--features", "2000000", "--warmup", "2", "--steps", "4"]
+    runs = []
+    for name in ("a", "b"):
+        d = str(tmp_path / name)
+        j = _bench_1gpu(base + ["--dump-outputs", d])
+        assert sorted(os.listdir(d)) == ["loss_sum.npy", "weight_keys.npy", "weights.npy"]
+        out = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+        n = 4096 * 39
+        assert out["loss_sum"].dtype == np.float64 and out["loss_sum"].shape == (1,)
+        assert out["weight_keys"].dtype == np.float64 and out["weight_keys"].shape == (n,)
+        assert out["weights"].dtype == np.float32 and out["weights"].shape == (n, 1)
+        assert j["steps"] == 4 and j["ms_per_step"] > 0
+        # the dumped loss is the last step's (the JSON line rounds its mean to 1e-5)
+        assert out["loss_sum"][0] / 4096 == pytest.approx(j["config"]["loss_last"], abs=1.1e-5)
+        k = out["weight_keys"]
+        assert (k >= 0).all() and (k < 2000000).all() and (k == np.floor(k)).all()
+        # every key of the batch was trained: its row exists and has moved off
+        # the (u - 0.5) * 0.01 initialiser's range somewhere
+        assert np.isfinite(out["weights"]).all() and np.abs(out["weights"]).max() > 0.005
+        runs.append(out)
+    a, b = runs
+    np.testing.assert_array_equal(a["weight_keys"], b["weight_keys"])
+    lr, eps = 0.05, 1e-8  # bench.py --lr, Optimizer.eps
+    np.testing.assert_allclose(a["weights"], b["weights"], rtol=0,
+                               atol=lr / np.sqrt(eps) * 8 * 2.0 ** -24)
+    np.testing.assert_allclose(a["loss_sum"], b["loss_sum"], rtol=1e-4)
 
 
 def _planted_corpus(path, clusters=20, words=40, sentences=6000, length=12, seed=5):
