@@ -353,6 +353,10 @@ class RoundEngine {
     if (!own_grad.empty() && (own_grad.size() != 4 || !own_grad[0] || !own_grad[1] ||
                               own_grad[2] < 1 || !self_bypass() || dim_ != 1))
       throw std::invalid_argument("push_xgmi: own_grad = (gs, spj, F, xval), scalar rows, bypass on");
+    // ... which only the fused scalar merge does, and not out of the staging
+    // buffer: refused before anything of the round is enqueued
+    if (!own_grad.empty() && table && (gstage || !(update && scalar_fused)))
+      throw std::invalid_argument("push_xgmi: own_grad needs the fused scalar merge, no staging");
     check_xgmi();
     std::vector<std::vector<long long>> parts;
     parts.push_back(part(grads, ucount, 0, 4ll * dim_, grads_[slot], cap_, self_bypass()));
@@ -376,8 +380,6 @@ class RoundEngine {
         sg.ind = Pt<const uint32_t>(own_grad[1]);
         sg.F = (uint32_t)own_grad[2];
         sg.xv = Pt<const float>(own_grad[3]);
-        if (gstage || !(update && scalar_fused))
-          throw std::invalid_argument("push_xgmi: own_grad needs the fused scalar merge, no staging");
       }
       // the peers' gradient rows streamed out of the uncached mailbox into a
       // cached buffer first: the merge gathers them per received position

@@ -176,6 +176,10 @@ class SparseLRWorker(PipelinedWorker):
             # servers merge per distinct key with the AdaGrad update fused
             o, eng = dd.owner, self.engine
             own = rnd.own_vals is not None and self.gring is not None
+            # ... and their gradients handed to the server merge in place,
+            # where this round's merge can read them (PSEngine.own_merge);
+            # else through the arena like the peers' (skip and own_grad agree)
+            og = own and eng.own_merge()
             gs = self.gring[slot] if own else self.gocc
             lo = eng.rank * o.ucap
             h.lr_fwd_g(0, xp, self.labels[slot].data_ptr(), d.batch_size, d.num_fields,
@@ -188,8 +192,8 @@ class SparseLRWorker(PipelinedWorker):
             h.rec_grad(dd.ucount.data_ptr(), eng.world, o.ucap, o.spj.data_ptr(),
                        gs.data_ptr(), xp, d.num_fields, rnd.ugrad.data_ptr(), st,
                        acc=self._acc.data_ptr(), acc_out=self.loss_sum.data_ptr(),
-                       acc_n=self._acc.numel(), skip=eng.rank if own else -1)
-            if own:
+                       acc_n=self._acc.numel(), skip=eng.rank if og else -1)
+            if og:
                 rnd.own_grad = (gs.data_ptr(), o.spj.data_ptr(), d.num_fields, xp)
         elif self.bucketed:
             o = dd.owner

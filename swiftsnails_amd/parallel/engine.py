@@ -521,7 +521,7 @@ class PSEngine(HostRounds, DeviceSetup, EngineControl):
             self._deferred_slot = slot
         svals = self.svals.data_ptr() if S is not None else 0
         ss = self._srv_stream(custom)
-        ov = self.own_vals[slot] if getattr(self, "own_vals", None) is not None else None
+        ov = self.own_vals[slot] if self.own_merge() else None
         self.native.pull_xgmi(slot, self._tag, st, False, -1, ahead and not custom, S is not None,
                               tab.dt if S else self._nodt, tab._init_native if S else self._noip,
                               tab.size_ctr.data_ptr() if S else 0, tab.err.data_ptr() if S else 0,
@@ -580,6 +580,20 @@ class PSEngine(HostRounds, DeviceSetup, EngineControl):
                 not getattr(tab, "bf16", False)):
             return "scalar"
         return None
+
+    def own_merge(self) -> bool:
+        """Record exchange: whether a round may take the own-record shortcut —
+        this rank's own records' rows in the cached ``own_vals`` buffer and
+        their gradients read by the server merge straight from the worker's
+        per-sample gradient (``Round.own_grad``).  Only the fused scalar
+        AdaGrad merge reads gradients that way, and not through the staging
+        buffer: every other rule (SGD, bf16 rows, a tensor-code push method,
+        SS_SRV_STAGE=1) sends its own records through the arena like the
+        peers'.  Asked per round — by the pull, by the worker's compute and by
+        the push — since a push method may be installed between rounds."""
+        return (getattr(self, "own_vals", None) is not None and
+                self._server_update_kind() == "scalar" and
+                getattr(self, "gstage", None) is None)
 
     def _srv_stream(self, host_side: bool) -> int:
         """hipStream_t of the server stream for this stage, 0 for none.  A
@@ -673,6 +687,12 @@ class PSEngine(HostRounds, DeviceSetup, EngineControl):
         elif self.xg and self.gpu:
             kind = self._server_update_kind()
             S = self.srv[slot] if self.srv is not None else None
+            if rnd.own_grad and not self.own_merge():
+                # the worker skipped its own records' gradient rows for a
+                # merge that can no longer read them in place (the update
+                # rule changed between the round's compute and its push)
+                raise RuntimeError("push: the round's own-record gradients need the fused "
+                                   "scalar merge; change the update rule between rounds")
             merged_only = S is not None and kind is None
             ss = self._srv_stream(merged_only)
             self.native.push_xgmi(slot, self._tag, self.raw_stream(), g.data_ptr(),

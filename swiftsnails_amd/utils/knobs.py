@@ -110,8 +110,9 @@ KNOBS: dict[str, Knob] = {
     "SS_REC_OCC": Knob("own", "parallel/engine_dist.py", "tuning",
                        "record exchange: own = this rank's own records' rows go to a cached "
                        "buffer and their gradients are read by the server merge through spj "
-                       "(never written per occurrence); arena = both through the mailbox, "
-                       "like the peers' records"),
+                       "(never written per occurrence) — in rounds the fused scalar AdaGrad "
+                       "merge serves, without staging; arena = both through the mailbox, "
+                       "like the peers' records (every other rule's rounds always)"),
     "SS_SRV_STAGE": Knob("0", "parallel/engine_dist.py", "tuning",
                          "1: N>1 xGMI servers stream the peers' gradient rows out of the "
                          "uncached mailbox into a cached buffer before the merge gathers them "
