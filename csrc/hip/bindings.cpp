@@ -8,6 +8,7 @@
 #include <pybind11/stl.h>
 
 #include "comm.h"
+#include "ss/evict.h"
 #include "worker.h"
 #include "ss_launch.h"
 
@@ -187,6 +188,24 @@ PYBIND11_MODULE(_ss_hip, m) {
 
   m.def("probe_hist", [](const DevTable& t, uintptr_t hist, int nbins, uintptr_t st) {
     launch_probe_hist(t, P<unsigned long long>(hist), nbins, S(st));
+  });
+
+  // ---- in-place eviction (evict.hip): mark, cluster repair, range clear
+  m.def("evict_mark", [](const DevTable& t, int use_w, float w_below, int use_acc, float acc_below,
+                         int opt_kind, uintptr_t mask, uintptr_t flag, uintptr_t rhas,
+                         uintptr_t nvict, uintptr_t st) {
+    launch_evict_mark(t, EvictRule{use_w, use_acc, w_below, acc_below}, opt_kind,
+                      P<const uint8_t>(mask), P<uint8_t>(flag), P<uint8_t>(rhas),
+                      P<unsigned long long>(nvict), S(st));
+  }, py::arg("t"), py::arg("use_w"), py::arg("w_below"), py::arg("use_acc"),
+     py::arg("acc_below"), py::arg("opt_kind"), py::arg("mask"), py::arg("flag"), py::arg("rhas"),
+     py::arg("nvict"), py::arg("st"));
+  m.def("evict_repair", [](const DevTable& t, uintptr_t flag, float state_init, uintptr_t st) {
+    launch_evict_repair(t, P<const uint8_t>(flag), state_init, S(st));
+  });
+  m.def("evict_clear", [](const DevTable& t, unsigned long long s0, long long n, uintptr_t flag,
+                          int victims_only, float state_init, uintptr_t st) {
+    launch_evict_clear(t, s0, n, P<const uint8_t>(flag), victims_only, state_init, S(st));
   });
 
   // ---- dedup / route (K1/K2/K6/K7)

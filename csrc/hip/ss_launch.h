@@ -63,6 +63,17 @@ void launch_export(const DevTable& t, unsigned long long s0, long long n, uint64
                    float* rows_out, unsigned long long* cursor, hipStream_t st);
 void launch_probe_hist(const DevTable& t, unsigned long long* hist, int nbins, hipStream_t st);
 
+// --- evict.hip: in-place eviction (ss/evict.h has the rule).  flag: one byte
+// per slot; rhas: one byte per region (zeroed by the caller; 1 = the region
+// has an EMPTY slot); nvict: a sharded counter ([kCtrShards x 128 B], zeroed)
+struct EvictRule;
+void launch_evict_mark(const DevTable& t, const EvictRule& rule, int opt_kind, const uint8_t* mask,
+                       uint8_t* flag, uint8_t* rhas, unsigned long long* nvict, hipStream_t st);
+void launch_evict_repair(const DevTable& t, const uint8_t* flag, float state_init,
+                         hipStream_t st);
+void launch_evict_clear(const DevTable& t, unsigned long long s0, long long n, const uint8_t* flag,
+                        int victims_only, float state_init, hipStream_t st);
+
 // --- dedup.hip
 struct RouteSpec {
   const int* frag_map;  // frag -> destination rank (device)

@@ -36,6 +36,8 @@ __device__ __forceinline__ long long probe_slot(const DevTable& t, uint64_t key,
     uint64_t* kp = slot_key(t, s);
     // A slot's key only ever changes EMPTY -> key inside a launch, so a stale
     // plain load can only read EMPTY; the CAS below then returns the truth.
+    // (The one exception, the eviction launches of evict.hip, empty and move
+    // keys — and never run beside a probe.)
     uint64_t k = *kp;
     if (k == key) return (long long)s;
     if (k == kEmptyKey) {

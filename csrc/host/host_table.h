@@ -16,6 +16,7 @@
 #include <cstring>
 #include <thread>
 #include <unordered_map>
+#include <unordered_set>
 #include <cstdio>
 #include <fstream>
 #include <memory>
@@ -26,6 +27,7 @@
 
 #include "channel.h"
 #include "common.h"
+#include "ss/evict.h"
 #include "ss/hash.h"
 #include "ss/optim.h"
 #include "string_util.h"
@@ -72,11 +74,38 @@ class HostShard : NonCopyable {
     for (size_t s = 0; s < cap_; ++s)
       if (keys_[s] != kEmptyKey) f(keys_[s], &rows_[s * width_]);
   }
+  // Drop every key with victim(key, row): the shard is rebuilt at its
+  // capacity from the survivors (rows unchanged), so linear probing finds
+  // each of them again.  Returns the number dropped.
+  template <class V>
+  size_t evict_if(V&& victim) {
+    bool any = false;  // nothing to drop: the shard stays as it is
+    for (size_t s = 0; s < cap_ && !any; ++s)
+      any = keys_[s] != kEmptyKey && victim(keys_[s], &rows_[s * width_]);
+    if (!any) return 0;
+    std::vector<uint64_t> ok;
+    std::vector<float> orows;
+    ok.swap(keys_);
+    orows.swap(rows_);
+    const size_t ocap = cap_, before = size_;
+    alloc(ocap);
+    for (size_t s = 0; s < ocap; ++s)
+      if (ok[s] != kEmptyKey && !victim(ok[s], &orows[s * width_]))
+        place(ok[s], &orows[s * width_]);
+    return before - size_;
+  }
   size_t size() const { return size_; }
   size_t capacity() const { return cap_; }
   std::mutex& mutex() { return mu_; }
 
  private:
+  void place(uint64_t key, const float* row) {
+    size_t t = fastrange64(table_hash(key), cap_);
+    while (keys_[t] != kEmptyKey) t = (t + 1 == cap_) ? 0 : t + 1;
+    keys_[t] = key;
+    std::copy(row, row + width_, &rows_[t * width_]);
+    ++size_;
+  }
   void alloc(size_t cap) {
     cap_ = cap;
     keys_.assign(cap, kEmptyKey);
@@ -91,13 +120,7 @@ class HostShard : NonCopyable {
     const size_t ocap = cap_;
     alloc(ocap * 2);
     for (size_t s = 0; s < ocap; ++s)
-      if (ok[s] != kEmptyKey) {
-        size_t t = fastrange64(table_hash(ok[s]), cap_);
-        while (keys_[t] != kEmptyKey) t = (t + 1 == cap_) ? 0 : t + 1;
-        keys_[t] = ok[s];
-        std::copy(&orows[s * width_], &orows[s * width_] + width_, &rows_[t * width_]);
-        ++size_;
-      }
+      if (ok[s] != kEmptyKey) place(ok[s], &orows[s * width_]);
   }
   int dim_, width_;
   size_t cap_ = 0, size_ = 0;
@@ -283,6 +306,40 @@ class HostTable : NonCopyable {
       if (r) std::copy(r, r + width_, rows + i * width_);
       else std::fill(rows + i * width_, rows + (i + 1) * width_, 0.f);
     });
+  }
+  // Forget the rows ss/evict.h's rule names (the HBM table's evict, same
+  // rule); each shard under its mutex.  Returns the number of keys removed.
+  size_t evict(const EvictRule& rule) {
+    SS_CHECK_MSG(rule.use_w || rule.use_acc, "evict: a rule needs w_below or acc_below");
+    const int acc_off = evict_acc_offset(op_.kind, dim_);
+    SS_CHECK_MSG(!rule.use_acc || acc_off >= 0,
+                 "evict: acc_below needs an optimizer with a sum-of-squares block");
+    std::vector<size_t> gone(shards_.size(), 0);
+    pool_->parallel_for((int)shards_.size(), [&](int s) {
+      auto& sh = *shards_[s];
+      std::lock_guard<std::mutex> lk(sh.mutex());
+      gone[s] = sh.evict_if([&](uint64_t, const float* row) {
+        return evict_victim(rule, (uint32_t)dim_, acc_off, [row](uint32_t j) { return row[j]; });
+      });
+    });
+    size_t n = 0;
+    for (size_t g : gone) n += g;
+    return n;
+  }
+  // Remove the given keys; keys the table does not hold are ignored.
+  size_t remove(const uint64_t* keys, size_t n) {
+    std::vector<std::unordered_set<uint64_t>> sets(shards_.size());
+    for (size_t i = 0; i < n; ++i) sets[to_shard_id(keys[i])].insert(keys[i]);
+    std::vector<size_t> gone(shards_.size(), 0);
+    pool_->parallel_for((int)shards_.size(), [&](int s) {
+      if (sets[s].empty()) return;
+      auto& sh = *shards_[s];
+      std::lock_guard<std::mutex> lk(sh.mutex());
+      gone[s] = sh.evict_if([&](uint64_t k, const float*) { return sets[s].count(k) != 0; });
+    });
+    size_t r = 0;
+    for (size_t g : gone) r += g;
+    return r;
   }
   size_t size() {
     size_t s = 0;

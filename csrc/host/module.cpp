@@ -209,6 +209,14 @@ PYBIND11_MODULE(_ss_host, m) {
         t.get_rows(k.data(), (size_t)k.size(), rows.mutable_data(), found.mutable_data());
         return py::make_tuple(rows, found);
       })
+      .def("evict", [](HostTable& t, int use_w, float w_below, int use_acc, float acc_below) {
+        py::gil_scoped_release rel;
+        return t.evict(EvictRule{use_w, use_acc, w_below, acc_below});
+      }, py::arg("use_w"), py::arg("w_below"), py::arg("use_acc"), py::arg("acc_below"))
+      .def("remove", [](HostTable& t, u64arr k) {
+        py::gil_scoped_release rel;
+        return t.remove(k.data(), (size_t)k.size());
+      })
       .def("export", [](HostTable& t) {
         std::vector<uint64_t> k;
         std::vector<float> r;

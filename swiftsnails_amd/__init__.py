@@ -6,7 +6,8 @@ Public API (mirrors the reference umbrella header /root/reference/src/swiftsnail
                  (host/TCP clusters) and ``PSContext``/``run_training`` (MI355X
                  collective mode, one process per GPU)
 * parameters   : ``HbmTable`` (GPU shard), ``HostTable`` (CPU shard),
-                 ``Optimizer`` / ``InitConfig`` (the Pull/PushAccessMethod menu)
+                 ``Optimizer`` / ``InitConfig`` (the Pull/PushAccessMethod menu),
+                 ``EvictRule`` (``table.evict``: forgetting cold keys in place)
 * access       : ``GlobalParamCache``, ``global_pull_access().pull_with_barrier``,
                  ``global_push_access().push_with_barrier`` (the reference's calls,
                  over a GPU engine or a host client); ``PSEngine.pull`` / ``push`` /
@@ -23,7 +24,7 @@ __version__ = "0.1.0"
 
 from .utils.config import Config, global_config  # noqa: E402
 from .parallel.router import HashFrag  # noqa: E402
-from .ops.optim import InitConfig, Optimizer  # noqa: E402
+from .ops.optim import EvictRule, InitConfig, Optimizer  # noqa: E402
 
 
 def __getattr__(name):  # lazy: GPU modules import torch/HIP on first use
@@ -57,7 +58,8 @@ def __getattr__(name):  # lazy: GPU modules import torch/HIP on first use
     raise AttributeError(name)
 
 
-__all__ = ["Config", "global_config", "HashFrag", "InitConfig", "Optimizer", "HbmTable",
-           "HostTable", "PSEngine", "SwiftMaster", "SwiftServer", "SwiftWorker", "BaseAlgorithm",
-           "PSContext", "run_training", "SparseLRWorker", "Word2VecWorker", "FMWorker", "DenseLR",
-           "GlobalParamCache", "global_pull_access", "global_push_access", "set_global_target"]
+__all__ = ["Config", "global_config", "HashFrag", "InitConfig", "Optimizer", "EvictRule",
+           "HbmTable", "HostTable", "PSEngine", "SwiftMaster", "SwiftServer", "SwiftWorker",
+           "BaseAlgorithm", "PSContext", "run_training", "SparseLRWorker", "Word2VecWorker",
+           "FMWorker", "DenseLR", "GlobalParamCache", "global_pull_access", "global_push_access",
+           "set_global_target"]

@@ -46,6 +46,32 @@ from ..utils.tracing import Tracer
 log = get_logger("swiftsnails.gpu")
 
 
+def evict_config(cfg) -> tuple:
+    """(period, rule, min_load) of the periodic eviction: ``evict_period``
+    (rounds, 0 = off), ``evict_acc_below`` / ``evict_w_below`` (the
+    ``EvictRule``; at least one when the period is set) and ``evict_min_load``
+    (a shard is evicted only at this load factor or above; default 0).
+    ``graph: 1`` with a period is refused: eviction between hipGraph replays
+    is not supported."""
+    from ..ops.optim import EvictRule
+
+    period = int(cfg.get("evict_period", 0) or 0)
+    if period <= 0:
+        return 0, None, 0.0
+    acc, w = cfg.get("evict_acc_below"), cfg.get("evict_w_below")
+    rule = EvictRule(w_below=float(w) if w not in (None, "") else None,
+                     acc_below=float(acc) if acc not in (None, "") else None)
+    if rule.w_below is None and rule.acc_below is None:
+        raise ValueError("evict_period is set: give evict_acc_below and / or evict_w_below")
+    if rule.acc_below is not None and str(cfg.get("optimizer", "adagrad")) == "sgd":
+        raise ValueError("evict_acc_below: SGD rows have no sum-of-squares block "
+                         "(use evict_w_below)")
+    if str(cfg.get("graph", "0")) not in ("0", "false", ""):
+        raise ValueError("evict_period > 0 cannot be combined with graph: 1 (eviction between "
+                         "hipGraph replays is not supported)")
+    return period, rule, float(cfg.get("evict_min_load", 0) or 0)
+
+
 def _ranks(spec, world: int) -> list[int]:
     if spec is None or str(spec).strip() in ("", "all"):
         return list(range(world))
@@ -103,6 +129,10 @@ class PSContext:
         self.backup_period = int(cfg.get("param_backup_period", 0) or 0)
         self._last_backup = -1
         self.backup_root = cfg.get("param_backup_root", ".")
+        # periodic in-place eviction of cold keys (maybe_evict)
+        self.evict_period, self.evict_rule, self.evict_min_load = evict_config(cfg)
+        self._last_evict = 0
+        self.evicted = 0  # keys this job evicted, all ranks
         self.ckpt_format = cfg.get("checkpoint_format", "bin")
         self.tracer = Tracer(enabled=str(cfg.get("trace", "0")) not in ("0", "false"))
         self.engine.tracer = self.tracer  # per-phase ranges: route / pull / compute / push
@@ -138,6 +168,7 @@ class PSContext:
             m = re.match(r".*param-(\d+)$", str(resume))
             self.start_round = int(m.group(1)) if m else 0
         self._last_backup = self.start_round  # the resumed state is already on disk
+        self._last_evict = self.start_round
 
     def _agree(self, found, store):
         """Rank 0's choice of checkpoint ``(prefix, round, world, fmt)``, for
@@ -198,6 +229,46 @@ class PSContext:
             if self.watchdog:
                 self.watchdog.resume()
 
+    def maybe_evict(self, round_idx: int, worker=None) -> Optional[int]:
+        """Every ``evict_period`` applied rounds (the crossed-a-boundary rule
+        of ``maybe_backup``): forget the keys the configured rule names
+        (``evict_acc_below`` / ``evict_w_below``) on every shard whose load
+        factor is at least ``evict_min_load``.  ``worker``: the job's
+        ``PipelinedWorker``; a pulled-ahead pipeline is switched to
+        synchronous rounds and drained first (those rounds train as usual)
+        and switched back after, on every rank alike, since the drain steps
+        are collective rounds.  Returns the keys evicted over all ranks (None
+        when it was not time); rank 0 logs it."""
+        p = self.evict_period
+        if not (p > 0 and round_idx > 0 and round_idx // p > max(self._last_evict, 0) // p):
+            return None
+        self._last_evict = round_idx
+        if self.watchdog:
+            self.watchdog.pause()
+        eng = self.engine
+        ahead = bool(getattr(eng, "pull_ahead", False))
+        if worker is not None and ahead:
+            worker.set_pull_ahead(False)
+        n = 0
+        tab = self.table
+        if worker is not None:
+            worker.drain()
+        if tab is not None and (self.evict_min_load <= 0 or
+                                tab.size() / tab.capacity >= self.evict_min_load):
+            n = (worker or eng).evict(rule=self.evict_rule)
+        if worker is not None and ahead:
+            worker.set_pull_ahead(True)
+        t = torch.tensor([n], dtype=torch.int64)
+        if self.world > 1:
+            dist.all_reduce(t)
+        n = int(t.item())
+        self.evicted += n
+        if self.rank == 0:
+            log.warning("round %d: evicted %d keys", round_idx, n)
+        if self.watchdog:
+            self.watchdog.resume()
+        return n
+
     def round_done(self, round_idx: int) -> None:
         """Per-round progress mark for the watchdog (+ fault injection point)."""
         if self.watchdog:
@@ -234,6 +305,7 @@ def build_worker(cfg: Config):
 
     model = cfg.get("model", "sparse_lr")
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    evict_config(cfg)  # a bad combination is refused before anything is built
     if str(cfg.get("graph", "0")) not in ("0", "false", ""):
         # hipGraph replays run the server half on the main stream: a server
         # stream that existed during the eager start-up made the replays of
@@ -348,6 +420,7 @@ def run_training(cfg: Config, steps: Optional[int] = None, warmup: int = 0,
         i += 1
         ctx.round_done(w.step_idx)
         ctx.maybe_backup(w.rounds_done())
+        ctx.maybe_evict(w.rounds_done(), w)
         if log_every and i % log_every == 0 and ctx.rank == 0:
             log.warning("step %d loss %.5f", i, w.mean_loss())
     steps = i
@@ -387,6 +460,8 @@ def run_training(cfg: Config, steps: Optional[int] = None, warmup: int = 0,
                         "mfma": ("none (fp32 dot products)" if w.per_pair else
                                  "bf16" if d.mode == "window" or w.mfma_bf16 else "fp32"),
                         "negatives": d.negatives}
+    if ctx.evict_period > 0:
+        stats["evict"] = {"period": ctx.evict_period, "evicted": ctx.evicted}
     m = ctx.engine.metrics.counters
     if m:
         stats["rank0_engine"] = {k: int(v) for k, v in m.items()}

@@ -342,6 +342,24 @@ class PipelinedWorker:
         while self._pulled and not self.engine.pull_ahead:
             self.step()
 
+    def evict(self, rule=None, mask=None) -> int:
+        """Forget cold keys of this rank's shard between steps
+        (``PSEngine.evict``); returns the number removed.  Drains a pipeline
+        that was switched to synchronous rounds first.  Raises while a round
+        is between its pull and its push (pulled-ahead rounds: their slot
+        indices would go stale; ``set_pull_ahead(False)`` first) and while
+        captured graphs are live (a replay holds ring slots across calls).
+        The routed lookahead round stays valid: routing reads no table
+        state."""
+        if self._graphs is not None:
+            raise RuntimeError("evict: the step is replayed from captured graphs; eviction "
+                               "between replays is not supported (close() the graphs first)")
+        self.drain()
+        if self._pulled:
+            raise RuntimeError(f"evict: {len(self._pulled)} pulled-ahead round(s) not pushed yet; "
+                               "switch to synchronous rounds (set_pull_ahead(False)) first")
+        return self.engine.evict(rule=rule, mask=mask)
+
     def calibrate_pull_ahead(self, steps: int = 10, windows: int = 2,
                              margin: float = 0.03) -> dict:
         """SS_PULL_AHEAD=auto at N>1: time synchronous and pulled-ahead steps

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from .._native import host
-from .optim import INIT_KINDS, OPT_KINDS, InitConfig, Optimizer
+from .optim import INIT_KINDS, OPT_KINDS, EvictRule, InitConfig, Optimizer
 
 
 def _host_init(c: InitConfig):
@@ -136,6 +136,22 @@ class HostTable:
         k, r = self._t.export()
         if len(k):
             yield torch.from_numpy(k.view(np.int64)), torch.from_numpy(r)
+
+    def evict(self, rule: Optional[EvictRule] = None, mask=None) -> int:
+        """Remove the rows ``rule`` names (``HbmTable.evict``, the same rule
+        code); returns the number removed.  A removed key that is pulled again
+        starts from its initial row.  The CPU table has no slot order to
+        address a ``mask`` by: use ``remove(keys)``."""
+        if mask is not None:
+            raise ValueError("HostTable.evict takes a rule; remove(keys) drops given keys")
+        if rule is None:
+            raise ValueError("evict: give a rule")
+        self._t.set_opt(_host_opt(self.opt))
+        return int(self._t.evict(*rule.native_args(self.opt)))
+
+    def remove(self, keys) -> int:
+        """Remove the given keys (missing ones are ignored); returns the count."""
+        return int(self._t.remove(_u64(keys).reshape(-1)))
 
     def size(self) -> int:
         return self._t.size()

@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
+from typing import Optional
 
 import numpy as np
 
@@ -90,6 +91,29 @@ class Optimizer:
         g = (lambda k, d: cfg.get(prefix + k, d)) if hasattr(cfg, "get") else (lambda k, d: d)
         return cls(kind=str(g("optimizer", "adagrad")), lr=float(g("learning_rate", 0.05)),
                    l1=float(g("l1", 0.0)), l2=float(g("l2", 0.0)))
+
+
+@dataclass
+class EvictRule:
+    """Which rows ``evict`` removes (csrc/include/ss/evict.h, one definition
+    for the HBM and the host table): a row is a victim iff every condition
+    that is set holds — ``w_below``: ``max_j |w_j| <= w_below`` over the
+    parameters; ``acc_below``: ``max_j acc_j <= acc_below`` over the
+    optimizer's sum-of-squares block (AdaGrad's accumulator, FTRL's ``n``,
+    Adam's ``v``; SGD has none).  Comparisons are on fp32 values; a NaN
+    coordinate keeps the row."""
+    w_below: Optional[float] = None
+    acc_below: Optional[float] = None
+
+    def native_args(self, opt: "Optimizer") -> tuple:
+        """(use_w, w_below, use_acc, acc_below) for the native calls, checked
+        against the table's optimizer."""
+        if self.w_below is None and self.acc_below is None:
+            raise ValueError("EvictRule: set w_below, acc_below or both")
+        if self.acc_below is not None and opt.kind == "sgd":
+            raise ValueError("EvictRule.acc_below: SGD rows have no sum-of-squares block")
+        return (int(self.w_below is not None), float(self.w_below or 0.0),
+                int(self.acc_below is not None), float(self.acc_below or 0.0))
 
 
 def init_reference(init: InitConfig, keys: np.ndarray, dim: int, width: int) -> np.ndarray:

@@ -28,7 +28,7 @@ import torch
 
 from ..utils.streams import current_raw
 from .._native import hip
-from .optim import InitConfig, Optimizer
+from .optim import OPT_KINDS, EvictRule, InitConfig, Optimizer
 
 EMPTY_I64 = -1  # u64 0xFFFF_FFFF_FFFF_FFFF
 CTR_SHARDS = 256  # == ss::kCtrShards
@@ -554,6 +554,95 @@ class HbmTable:
             self.resize(int(max(self.capacity * factor, (self.size() + incoming) / 0.5)))
             return True
         return False
+
+    # -- eviction -----------------------------------------------------------
+    def evict(self, rule: Optional[EvictRule] = None, mask: Optional[torch.Tensor] = None,
+              stream=None) -> int:
+        """Remove cold keys in place and give their slots back; returns the
+        number removed (syncs the stream).
+
+        ``rule``: an ``EvictRule`` evaluated on every stored row; or ``mask``:
+        a bool tensor [capacity] in slot order (``keys_view()`` /
+        ``rows_view()``), the victims as tensor code names them (bits on EMPTY
+        slots are ignored).  Exactly one of the two.
+
+        Survivors keep their rows bit for bit (some move to another slot:
+        evict.hip repairs each probe cluster that lost a key), a vacated slot
+        looks like a never-used one, and a removed key that is pulled again
+        starts from its initial row like any new key.  ``version`` grows, so
+        every pull snapshot is stale.  The table-full bit of ``err`` is
+        cleared iff every region that had no empty slot got one back.  No
+        probe may run beside this call: a caller with pulls on other streams
+        orders them first (``PSEngine.evict``).  Temporary memory: one byte
+        per slot (+ the caller's mask), except for regions without any empty
+        slot, which are rebuilt through a buffer of their survivors."""
+        if (rule is None) == (mask is None):
+            raise ValueError("evict: give exactly one of rule= and mask=")
+        use_w, w_below, use_acc, acc_below = (0, 0.0, 0, 0.0) if rule is None else \
+            rule.native_args(self.opt)
+        if stream is None:
+            ts = torch.cuda.current_stream(self.device)
+        elif isinstance(stream, int):
+            ts = torch.cuda.ExternalStream(stream, device=self.device)
+        else:
+            ts = stream
+        h, cap = hip(), self.capacity
+        mptr = 0
+        if mask is not None:
+            if mask.numel() != cap:
+                raise ValueError(f"evict: mask has {mask.numel()} entries, the table {cap} slots")
+            mask = mask.reshape(-1).to(self.device, torch.bool).contiguous()
+            mptr = mask.data_ptr()
+        R = 1 << self.rbits
+        rlen = cap // R
+        si = float(self.init_cfg.state_init)
+        with torch.cuda.stream(ts):
+            st = ts.cuda_stream
+            flag = torch.empty(cap, dtype=torch.uint8, device=self.device)
+            rhas = torch.zeros(R, dtype=torch.uint8, device=self.device)
+            nv = torch.zeros(CTR_SHARDS * 16, dtype=torch.int64, device=self.device)
+            h.evict_mark(self.dt, use_w, w_below, use_acc, acc_below, OPT_KINDS[self.opt.kind],
+                         mptr, flag.data_ptr(), rhas.data_ptr(), nv.data_ptr(), st)
+            self.version += 1
+            gone = int(nv.sum().item())
+            if gone == 0:
+                return 0
+            h.evict_repair(self.dt, flag.data_ptr(), si, st)
+            # regions without an EMPTY slot have no cluster boundary: rebuilt
+            # from their survivors
+            moved, freed_all = 0, True
+            for r in (rhas == 0).nonzero().reshape(-1).tolist():
+                lo = r * rlen
+                if not bool((flag[lo:lo + rlen] & 2).any()):
+                    freed_all = False  # still full: nothing of it was a victim
+                    continue
+                h.evict_clear(self.dt, lo, rlen, flag.data_ptr(), 1, si, st)
+                kbuf = torch.empty(rlen, dtype=torch.int64, device=self.device)
+                rbuf = torch.empty((rlen, self.width), dtype=torch.float32, device=self.device)
+                cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
+                h.export_slots(self.dt, lo, rlen, kbuf.data_ptr(), rbuf.data_ptr(),
+                               cursor.data_ptr(), st)
+                m = int(cursor.item())
+                h.evict_clear(self.dt, lo, rlen, flag.data_ptr(), 0, si, st)
+                if m:
+                    h.assign(self.dt, kbuf.data_ptr(), rbuf.data_ptr(), m,
+                             self.size_ctr.data_ptr(), self.err.data_ptr(), self.G, st)
+                moved += m
+            self.size_ctr[0] -= gone + moved  # the re-assign counted its keys again
+            if freed_all:
+                self.err.bitwise_and_(~1)
+        return gone
+
+    def remove(self, keys: torch.Tensor, stream=None) -> int:
+        """Evict the given keys; keys the table does not hold are ignored.
+        Returns the number removed."""
+        keys = keys.reshape(-1).to(self.device, torch.int64).contiguous()
+        if keys.numel() == 0:
+            return 0
+        slots = self.lookup_slots(keys, insert=False, stream=stream)
+        mask = torch.zeros(self.capacity, dtype=torch.bool, device=self.device)
+        mask[slots[slots >= 0]] = True
+        return self.evict(mask=mask, stream=stream)
 
     # -- dense views (tests / small tables) --------------------------------
     def to_dict(self, with_state: bool = False) -> dict[int, np.ndarray]:

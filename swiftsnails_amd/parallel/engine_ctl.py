@@ -188,6 +188,57 @@ class EngineControl:
         r[torch.from_numpy(found == 0)] = 0.0
         return r
 
+    # ------------------------------------------------------------ eviction
+    def evict(self, rule=None, mask=None) -> int:
+        """Forget cold keys of this rank's shard in place (``HbmTable.evict``
+        / ``HostTable.evict``: an ``EvictRule``, or on the GPU a bool ``mask``
+        over the slots); returns the number removed, 0 on a rank without a
+        table.  Not a collective: shards are independent, and a worker holds
+        no slot across rounds.
+
+        On the GPU the call first commits outstanding claimed pulls, then
+        makes the main stream wait for the pull, route and server streams (no
+        probe may run beside the eviction launches) and those streams for the
+        eviction.  The table's ``version`` grows, so every pull snapshot is
+        stale.  A claimed round that is pulled but not pushed yet keeps
+        working: survivors may have moved, so its keys are looked up again
+        (slots, rows and snapshot rewritten; a key of it that was evicted
+        restarts from its initial row).  Any other pulled round holds stale
+        slots: push it first (``PipelinedWorker.evict`` refuses otherwise)."""
+        tab = self.table
+        if tab is None:
+            return 0
+        if not self.gpu:
+            n = tab.evict(rule=rule, mask=mask)
+            self.metrics.add(evicted=n)
+            return n
+        from .engine import _hip
+
+        st = self.raw_stream()
+        held = list(getattr(self, "_claimed", None) or [])
+        if held:
+            self._commit_claimed(st)
+        main = self.main_stream()
+        side = [s for s in (getattr(self, "pull_stream", None),
+                            getattr(self, "route_stream", None),
+                            getattr(self, "server_stream", None)) if s is not None]
+        for s in side:
+            main.wait_stream(s)
+        n = tab.evict(rule=rule, mask=mask)
+        for rnd in held:
+            if rnd.pushed or rnd.applied:
+                continue
+            v = rnd.dd.owner.bucket_view(rnd.dd.n)
+            _hip().pull_unique_bk(tab.dt, v[0], v[1], v[2], v[3], v[4], rnd.slots.data_ptr(),
+                                  rnd.uvals.data_ptr(), tab._init_native, tab.size_ctr.data_ptr(),
+                                  tab.err.data_ptr(), tab.G, st, rnd.snap.data_ptr(),
+                                  int(bool(rnd.slot32)))
+            rnd.snap_version = tab.version
+        for s in side:
+            s.wait_stream(main)
+        self.metrics.add(evicted=n)
+        return n
+
     # ------------------------------------------------------------ control
     def barrier(self):
         self.t.barrier()
