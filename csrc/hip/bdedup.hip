@@ -1044,70 +1044,6 @@ template <int K>
 struct FmCols {
   static constexpr int v = (K + 1) * kBdTS * 4 <= 150 * 1024 ? K : 8;
 };
-// Fused K5 for a DIM-wide row whose merged gradient is in registers: the
-// optimizer update as one read-modify-write of the row (one thread per row;
-// the DIM coordinates and their state stay in registers).  The model kernels
-// below call it instead of storing ugrad when the engine fuses the apply
-// (PSEngine.fuse_apply: one GPU, compact unique ids).
-// FM k = 8 rows in fp32 keyfirst slots (80 bytes: [key | w_0..w_8 | s_0..s_8]
-// with one state word per coordinate, AdaGrad / SGD-state layouts): the 72-byte
-// row moves as one 8-byte and four 16-byte accesses per thread, all five loads
-// in flight together, instead of 18 dependent-address 4-byte row_ld / row_st
-// (the one-thread-per-row update that measured 0.62 -> 1.04 ms per FM step)
-__device__ __forceinline__ bool fm9_vec_ok(const DevTable& t, const OptParams& op) {
-  return !t.bf16 && t.dim == 9 && t.stride == 80 && t.row_off == 8 &&
-         opt_state_per_coord(op.kind) == 1;
-}
-__device__ __forceinline__ void fm9_row_update(const DevTable& t, long long slot,
-                                               const float (&g)[9], const OptParams& op) {
-  float* row = slot_row(t, (uint64_t)slot);  // 8-byte aligned; row + 2 is 16-byte aligned
-  float r[18];
-  const float2 a = *reinterpret_cast<const float2*>(row);
-  const float4* q4 = reinterpret_cast<const float4*>(row + 2);
-  float4 q[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) q[i] = q4[i];
-  r[0] = a.x, r[1] = a.y;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    r[2 + 4 * i] = q[i].x, r[3 + 4 * i] = q[i].y, r[4 + 4 * i] = q[i].z, r[5 + 4 * i] = q[i].w;
-  float s2 = 0.f;
-#pragma unroll
-  for (int j = 0; j < 9; ++j) opt_update(op, r[j], r[9 + j], s2, g[j]);
-  *reinterpret_cast<float2*>(row) = make_float2(r[0], r[1]);
-  float4* o4 = reinterpret_cast<float4*>(row + 2);
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    o4[i] = make_float4(r[2 + 4 * i], r[3 + 4 * i], r[4 + 4 * i], r[5 + 4 * i]);
-}
-
-template <int DIM>
-__device__ __forceinline__ void fused_row_update(const DevTable& t, long long slot,
-                                                 const float (&g)[DIM], const OptParams& op) {
-  if (slot < 0) return;
-  if constexpr (DIM == 9) {
-    if (fm9_vec_ok(t, op)) {
-      fm9_row_update(t, slot, g, op);
-      return;
-    }
-  }
-  const int ns = opt_state_per_coord(op.kind);
-  float w[DIM], s1[DIM], s2[DIM];
-#pragma unroll
-  for (int j = 0; j < DIM; ++j) {
-    w[j] = row_ld(t, slot, j);
-    s1[j] = ns > 0 ? row_ld(t, slot, DIM + j) : 0.f;
-    s2[j] = ns > 1 ? row_ld(t, slot, 2 * DIM + j) : 0.f;
-  }
-#pragma unroll
-  for (int j = 0; j < DIM; ++j) {
-    opt_update(op, w[j], s1[j], s2[j], g[j]);
-    row_st(t, slot, j, w[j], true);
-    if (ns > 0) row_st(t, slot, DIM + j, s1[j], true);
-    if (ns > 1) row_st(t, slot, 2 * DIM + j, s2[j], true);
-  }
-}
-
 template <int DIM, int NCOLS = 0>
 __global__ __launch_bounds__(1024) void k_bd_reduce_fm(const uint32_t* __restrict__ bstart,
                                                        const uint32_t* __restrict__ ubase,
@@ -1118,10 +1054,7 @@ __global__ __launch_bounds__(1024) void k_bd_reduce_fm(const uint32_t* __restric
                                                        const float* __restrict__ gss, int F,
                                                        const float* __restrict__ uvals,
                                                        float* __restrict__ ugrad,
-                                                       const uint32_t* __restrict__ blist,
-                                                       DevTable t = DevTable{},
-                                                       const long long* __restrict__ slots = nullptr,
-                                                       OptParams op = OptParams{}) {
+                                                       const uint32_t* __restrict__ blist) {
   constexpr int K = DIM - 1;
   constexpr int NC = NCOLS > 0 ? (NCOLS < K ? NCOLS : K) : FmCols<K>::v;
   __shared__ float g0[kBdTS];
@@ -1204,16 +1137,6 @@ __global__ __launch_bounds__(1024) void k_bd_reduce_fm(const uint32_t* __restric
     }
     __syncthreads();
   }
-  if (slots) {
-    // fused K5 (single column pass group, gridDim.y == 1): this workgroup's
-    // rows of ugrad are complete after the barrier above
-    for (uint32_t l = threadIdx.x; l < nu; l += 1024) {
-      float g[DIM];
-#pragma unroll
-      for (int j = 0; j < DIM; ++j) g[j] = ugrad[(size_t)(base + l) * DIM + j];
-      fused_row_update<DIM>(t, slots[base + l], g, op);
-    }
-  }
 }
 
 // compact unique rows (ubase[b] + l, the alltoallv layout) -> occurrence-space
@@ -1248,8 +1171,7 @@ __global__ __launch_bounds__(1024) void k_bd_reduce_fm_sorted(
     const uint32_t* __restrict__ unum, const uint32_t* __restrict__ pj,
     const uint32_t* __restrict__ luid, const float* __restrict__ gs,
     const float* __restrict__ gss, int F, const float* __restrict__ uvals,
-    float* __restrict__ ugrad, uint32_t* __restrict__ ovf, DevTable t,
-    const long long* __restrict__ slots, OptParams op) {
+    float* __restrict__ ugrad, uint32_t* __restrict__ ovf) {
   constexpr int K = DIM - 1;
   __shared__ uint32_t cnt[kBdTS];      // counts, then placement cursors
   __shared__ uint32_t seg[kBdTS + 1];  // list starts (exclusive scan of the counts)
@@ -1318,23 +1240,10 @@ __global__ __launch_bounds__(1024) void k_bd_reduce_fm_sorted(
   };
   auto store_row = [&](uint32_t l, float g0, const float* a) {
     const size_t r = (size_t)(base + l) * DIM;
-    if (slots) {  // fused K5: the row's update instead of its gradient store
-      float g[DIM];
-      g[0] = g0;
-#pragma unroll
-      for (int k = 0; k < K; ++k) g[1 + k] = a[k] - uvals[r + 1 + k] * g0;
-      fused_row_update<DIM>(t, slots[base + l], g, op);
-      return;
-    }
     ugrad[r] = g0;
 #pragma unroll
     for (int k = 0; k < K; ++k) ugrad[r + 1 + k] = a[k] - uvals[r + 1 + k] * g0;
   };
-  // fused FM k = 8 update with vector rows: the key's slot, its table row
-  // and its pulled v go out BEFORE the occurrence gathers, so the row's
-  // read latency overlaps the sum instead of following it
-  bool vec9 = false;
-  if constexpr (DIM == 9) vec9 = slots != nullptr && fm9_vec_ok(t, op);
   // short lists: a thread per unique key
   for (uint32_t l = tid; l < nu; l += 1024) {
     const uint32_t q0 = seg[l], q1 = seg[l + 1];
@@ -1342,38 +1251,6 @@ __global__ __launch_bounds__(1024) void k_bd_reduce_fm_sorted(
     float g0 = 0.f, a[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) a[k] = 0.f;
-    if constexpr (DIM == 9) {
-      if (vec9) {
-        const long long slot = slots[base + l];
-        const size_t r = (size_t)(base + l) * DIM;
-        float v[K], row[18];
-#pragma unroll
-        for (int k = 0; k < K; ++k) v[k] = uvals[r + 1 + k];
-        float* rp = slot >= 0 ? slot_row(t, (uint64_t)slot) : nullptr;
-        if (rp) {
-          const float2 x = *reinterpret_cast<const float2*>(rp);
-          const float4* q4 = reinterpret_cast<const float4*>(rp + 2);
-          row[0] = x.x, row[1] = x.y;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const float4 y = q4[i];
-            row[2 + 4 * i] = y.x, row[3 + 4 * i] = y.y, row[4 + 4 * i] = y.z, row[5 + 4 * i] = y.w;
-          }
-        }
-        accumulate(q0, q1, 1u, g0, a);
-        if (!rp) continue;
-        float s2 = 0.f;
-        opt_update(op, row[0], row[9], s2, g0);
-#pragma unroll
-        for (int k = 0; k < K; ++k) opt_update(op, row[1 + k], row[10 + k], s2, a[k] - v[k] * g0);
-        *reinterpret_cast<float2*>(rp) = make_float2(row[0], row[1]);
-        float4* o4 = reinterpret_cast<float4*>(rp + 2);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          o4[i] = make_float4(row[2 + 4 * i], row[3 + 4 * i], row[4 + 4 * i], row[5 + 4 * i]);
-        continue;
-      }
-    }
     accumulate(q0, q1, 1u, g0, a);
     store_row(l, g0, a);
   }
@@ -1887,17 +1764,8 @@ long long bd_fm_ovf_words(long long n) { return n / kFmOcc + 2; }
 void launch_bd_reduce_fm(long long n, int nranks, const uint32_t* scratch, const uint32_t* pj,
                          const uint32_t* luid, const float* gs, const float* gss, int F, int dim,
                          const float* uvals, float* ugrad, hipStream_t st, uint32_t* ovf,
-                         const DevTable* t, const long long* slots, const OptParams* op,
                          int ndest) {
   if (n <= 0) return;
-  DevTable tv{};
-  OptParams opv{};
-  if (slots) {
-    if (!t || !op || !ovf || t->dim != (uint32_t)dim)
-      throw_error("bd_reduce_fm: fused apply needs the table, the optimizer, the sorted path");
-    tv = *t;
-    opv = *op;
-  }
   const BdLayout L = bd_layout(n, nranks, ndest);
   const uint32_t* S = scratch;
   // default: sorted lists (no float atomics) + LDS-atomic form for overflow
@@ -1906,8 +1774,6 @@ void launch_bd_reduce_fm(long long n, int nranks, const uint32_t* scratch, const
     const char* e = std::getenv("SS_FM_REDUCE");
     return !(e && std::string(e) == "atomic");
   }();
-  if (slots && !(ovf && sorted))
-    throw_error("bd_reduce_fm: fused apply runs on the sorted path only (SS_FM_REDUCE)");
   if (ovf && sorted) {
     const int novf = (int)(n / kFmOcc) + 1;  // an overflow bucket holds > kFmOcc keys
     check_hip(hipMemsetAsync(ovf, 0, sizeof(uint32_t), st), "fm ovf count");
@@ -1915,11 +1781,9 @@ void launch_bd_reduce_fm(long long n, int nranks, const uint32_t* scratch, const
 #define SS_BDFMS_CASE(DD)                                                                      \
   case DD:                                                                                     \
     hipLaunchKernelGGL(k_bd_reduce_fm_sorted<DD>, dim3(L.P), dim3(1024), 0, st, S + L.bstart,  \
-                       S + L.ubase, S + L.unum, pj, luid, gs, gss, F, uvals, ugrad, ovf, tv,   \
-                       slots, opv);                                                            \
+                       S + L.ubase, S + L.unum, pj, luid, gs, gss, F, uvals, ugrad, ovf);      \
     hipLaunchKernelGGL(k_bd_reduce_fm<DD>, dim3(novf), dim3(1024), 0, st, S + L.bstart,         \
-                       S + L.ubase, S + L.unum, pj, luid, gs, gss, F, uvals, ugrad, ovf, tv,   \
-                       slots, opv);                                                            \
+                       S + L.ubase, S + L.unum, pj, luid, gs, gss, F, uvals, ugrad, ovf);      \
     break;
       SS_BDFMS_CASE(2)
       SS_BDFMS_CASE(5)

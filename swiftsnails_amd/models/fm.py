@@ -14,7 +14,6 @@ other beyond the lockstep collective round.
 """
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import numpy as np
@@ -90,23 +89,15 @@ class FMWorker(PipelinedWorker):
             # the sorted per-bucket merge sums each unique key's gradient row
             # once and stores it; the AdaGrad update is the separate lane-group
             # apply (k_apply_st, ~140 us: the random read-modify-write floor
-            # of 1.35M 72-byte rows).  SS_FM_FUSE=1 fuses the update into the
-            # merge instead — the row moved as 8- + 16-byte vectors per thread,
-            # its loads issued before the occurrence gathers (bdedup.hip
-            # fm9_row_update): measured 0.570-0.573 vs 0.542-0.546 ms per step
-            # (two A/B pairs, round 6; the scalar fused form: 0.62 -> 1.04 ms),
+            # of 1.35M 72-byte rows).  Fusing the update into the merge measured
+            # slower twice (0.570-0.573 vs 0.542-0.546 ms per step with vector
+            # rows, 0.62 -> 1.04 ms scalar; profiles/raw/r6_fm_fused_ab.txt) —
             # the extra row registers cost the merge's occupancy more than the
-            # gradient-row round trip it saves
-            fa = (self.engine.fuse_apply(rnd, snapshot=False)
-                  if os.environ.get("SS_FM_FUSE", "0") == "1" else None)
-            kw = {}
-            if fa is not None:
-                assert not fa["slot32"]  # FM slots are never 4-byte (slot32: scalar rows)
-                kw = {"t": fa["t"], "slots": fa["slots"], "op": fa["op"]}
+            # gradient-row round trip it saves — and was removed
             h.bd_reduce_fm(dd.lay, dd.nranks, o.scratch.data_ptr(), o.pj.data_ptr(),
                            o.luid.data_ptr(), self.gs.data_ptr(), self.gss.data_ptr(),
                            d.num_fields, self.engine.dim, rnd.uvals.data_ptr(),
-                           rnd.ugrad.data_ptr(), st, self.ovf.data_ptr(), ndest=o.ndest, **kw)
+                           rnd.ugrad.data_ptr(), st, self.ovf.data_ptr(), ndest=o.ndest)
             return
         hip().fm_fwd_bwd(rnd.inv.data_ptr(), self.labels[slot].data_ptr(), d.batch_size,
                          d.num_fields, self.engine.dim, rnd.uvals.data_ptr(),
