@@ -47,6 +47,10 @@ class FMWorker(PipelinedWorker):
                  active: bool = True):
         if engine.dim not in (2, 5, 9, 17):
             raise ValueError("FMWorker: dim must be 1+K with K in {1,4,8,16}")
+        if getattr(data, "has_values", False):
+            # the kernels are binary-feature: idx:val entries would be trained as val = 1
+            raise ValueError("FMWorker: the FM kernels take binary features; this source has "
+                             "feature values (idx:val), which they would ignore")
         super().__init__(engine, rank, world, active)
         self.data = data
         # the route stream is the light one for this model: pull the next

@@ -308,6 +308,26 @@ class Deduper:
                                                                   self.nranks, self.ndest)
         return [self.pos_of.data_ptr(), self.luid.data_ptr(), self.bkt.data_ptr(), ub]
 
+    def unique_ids(self, n: Optional[int] = None) -> torch.Tensor:
+        """uid(j) of the last call's keys j < n as int64 (-1 where a key has
+        none: EMPTY keys), computed from the BdIndex arrays; read-only (for
+        tests that read a round's pulled rows by key; syncs nothing itself).
+        Indices are clamped into their arrays, not validated: a corrupt
+        ``pos_of`` / ``luid`` / ``bkt`` entry yields a plausible id, so a
+        caller checks what it needs (one id per key, none for EMPTY)."""
+        if self.mode != "bucket":
+            raise RuntimeError("unique_ids needs mode='bucket'")
+        n = self._last_n if n is None else n
+        o_ub = self.h.bd_ubase_offset(max(1, self._lay(n)), self.nranks, self.ndest)
+        m32 = 0xFFFFFFFF
+        pos = self.pos_of[:n].long() & m32
+        bad = pos == m32
+        lu = self.luid[pos.clamp(max=self.luid.numel() - 1)].long() & m32
+        bad |= lu == m32
+        b = (self.bkt[:n].long() & m32).clamp(max=self.scratch.numel() - 1 - o_ub)
+        uid = (self.scratch[o_ub + b].long() & m32) + lu
+        return torch.where(bad, torch.full_like(uid, -1), uid)
+
     def bucket_view(self, n: Optional[int] = None):
         """(bkeys, bstart, unum, ubase, P) of the last call: bucket b's unique
         keys are bkeys[bstart[b] : bstart[b] + unum[b]] with unique ids from

@@ -286,6 +286,29 @@ def test_fm_fwd_bwd_matches_reference(dev, dim):
     np.testing.assert_allclose(g.cpu().numpy().reshape(B, F, dim), gr, rtol=1e-3, atol=1e-5)
 
 
+def _fm_grad_reference(inv, uvals, y, B, F):
+    """(G, eG, cnt) of ``_fm_oracle.key_gradient``: the fp64 per-key gradient
+    rows of one batch from the unique rows, the labels and each occurrence's
+    unique id, with the oracle's per-key bound.
+
+    Measured on an MI355X, max |kernel - fp64| / eG (row atomics / LDS atomics
+    / sorted lists; each test prints its own as ``MARGIN ...``):
+
+        bucket reduce  dim 9   0.543 all three      dim 17  0.749 all three
+                       dim 5, 3 ranks  0.209 / 0.199 / 0.177 (per rank, all three)
+        overflow       dim 2   0.200    dim 5  0.186 / 0.169 / 0.169
+                       dim 9   0.174 / 0.189 / 0.189        dim 17  0.255
+        bucket of 10240  0.159 / 0.142 / 0.142    of 10241  0.155 / 0.151 / 0.151
+
+    The fp32 NumPy evaluation at the bucket-reduce sizes sits at 0.229 (dim 9)
+    and 0.841 (dim 17, ``test_fm_oracle_cpu.py::test_key_gradient_fp32_floor``):
+    the dim-17 bucket-reduce case has the least headroom, watch it."""
+    import _fm_oracle as O
+
+    uid = inv.cpu().numpy().astype(np.int32).astype(np.int64).reshape(B, F)
+    return O.key_gradient(uid, uvals.cpu().numpy(), y.cpu().numpy())
+
+
 @pytest.mark.parametrize("dim,nranks", [(9, 1), (5, 3), (17, 1)])
 def test_fm_bucket_reduce_matches_atomic_path(dev, dim, nranks):
     """Atomic-free FM (lane-group forward + per-bucket LDS row reduction) ==
@@ -328,9 +351,18 @@ def test_fm_bucket_reduce_matches_atomic_path(dev, dim, nranks):
                    ovf.data_ptr(), ndest=d.ndest)
     torch.cuda.synchronize()
     uc = r.ucount.cpu().numpy()
+    # every kernel against the fp64 gradient, within the per-key bound of
+    # _fm_oracle.py (term accuracy + |O| 2^-24 A over the factored form)
+    G, eG, cnt = _fm_grad_reference(r.inv, uvals, y, B, F)
     for q in range(nranks):
         a, b = q * d.ucap, q * d.ucap + uc[q]
+        assert (cnt[a:b] > 0).all() and cnt[b:(q + 1) * d.ucap].sum() == 0
         ref = g_at[a:b].cpu().numpy()
+        for label, got in (("row atomics", ref), ("LDS atomics", g_b[a:b].cpu().numpy()),
+                           ("sorted lists", g_s[a:b].cpu().numpy())):
+            ratio = np.abs(got - G[a:b]) / eG[a:b]
+            print(f"MARGIN fm reduce dim {dim} nranks {nranks} {label}: {ratio.max():.3f}")
+            assert ratio.max() <= 1, (label, ratio.max())
         for got in (g_b[a:b].cpu().numpy(), g_s[a:b].cpu().numpy()):
             # fp32 sums in different orders (LDS atomics, sorted lists, global
             # atomics): a Zipf-head key sums hundreds of mixed-sign terms, so
@@ -341,25 +373,20 @@ def test_fm_bucket_reduce_matches_atomic_path(dev, dim, nranks):
     np.testing.assert_allclose(l_b.sum().item(), l_at.sum().item(), rtol=1e-4)
 
 
-@pytest.mark.parametrize("dim", [5, 9])
-def test_fm_sorted_reduce_overflow_buckets(dev, dim):
-    """Sorted-list FM reduce with buckets too large to sort in LDS (a key
-    with 30K occurrences): those go to the LDS-atomic form; both == the
-    per-occurrence atomic kernel."""
+def _fm_three_reduces(dev, keys, B, F, dim, seed):
+    """One batch through the three FM gradient kernels: returns (dedup result,
+    deduper, uvals, y, row-atomic / LDS-atomic / sorted-list gradients, ovf)."""
     from swiftsnails_amd._native import hip
     from swiftsnails_amd.ops.dedup import Deduper
 
     h = hip()
-    B, F = 16000, 8
     n = B * F
-    rng = np.random.default_rng(17)
-    keys = rng.integers(0, 1 << 40, size=n).astype(np.int64)
-    keys[rng.random(n) < 0.25] = 12345  # ~32K occurrences of one key
+    rng = np.random.default_rng(seed)
     d = Deduper(n, nranks=1, gdim=dim, device=dev, mode="bucket")
     r = d(torch.from_numpy(keys).to(dev))
     st = torch.cuda.current_stream().cuda_stream
     U = d.ucap
-    uvals = torch.randn(U, dim, device=dev) * 0.1
+    uvals = torch.from_numpy((rng.standard_normal((U, dim)) * 0.1).astype(np.float32)).to(dev)
     y = torch.from_numpy((rng.random(B) < 0.4).astype(np.float32)).to(dev)
     g_at = torch.zeros(U, dim, device=dev)
     h.fm_fwd_bwd(r.inv.data_ptr(), y.data_ptr(), B, F, dim, uvals.data_ptr(), g_at.data_ptr(),
@@ -368,16 +395,82 @@ def test_fm_sorted_reduce_overflow_buckets(dev, dim):
     gss = torch.empty(B * (dim - 1), device=dev)
     h.fm_fwd_g(0, d.index_ptrs(n), y.data_ptr(), B, F, dim,
                uvals.data_ptr(), gs.data_ptr(), gss.data_ptr(), 0, 0, st)
+    g_b = torch.full((U, dim), float("nan"), device=dev)
+    h.bd_reduce_fm(n, 1, d.scratch.data_ptr(), d.pj.data_ptr(), d.luid.data_ptr(),
+                   gs.data_ptr(), gss.data_ptr(), F, dim, uvals.data_ptr(), g_b.data_ptr(), st,
+                   ndest=d.ndest)
     ovf = torch.zeros(h.bd_fm_ovf_words(n), dtype=torch.int32, device=dev)
     g_s = torch.full((U, dim), float("nan"), device=dev)
     h.bd_reduce_fm(n, 1, d.scratch.data_ptr(), d.pj.data_ptr(), d.luid.data_ptr(),
                    gs.data_ptr(), gss.data_ptr(), F, dim, uvals.data_ptr(), g_s.data_ptr(), st,
                    ovf.data_ptr(), ndest=d.ndest)
     torch.cuda.synchronize()
+    d.check()
+    return r, d, uvals, y, g_at, g_b, g_s, ovf
+
+
+def _assert_fm_within_fp64_bound(label, r, uvals, y, B, F, grads):
+    u = int(r.ucount[0])
+    G, eG, cnt = _fm_grad_reference(r.inv, uvals, y, B, F)
+    assert (cnt[:u] > 0).all() and cnt[u:].sum() == 0
+    for kind, g in grads:
+        ratio = np.abs(g[:u].cpu().numpy() - G[:u]) / eG[:u]
+        print(f"MARGIN {label} {kind}: {ratio.max():.3f} (largest list {cnt.max()})")
+        assert ratio.max() <= 1, (label, kind, ratio.max())
+
+
+@pytest.mark.parametrize("dim", [2, 5, 9, 17])
+def test_fm_sorted_reduce_overflow_buckets(dev, dim):
+    """Sorted-list FM reduce with buckets too large to sort in LDS (a key
+    with 30K occurrences): those go to the LDS-atomic form; all three kernels
+    within the fp64 gradient's per-key bound, and the sorted form == the
+    per-occurrence atomic kernel as before."""
+    B, F = (16000, 8) if dim < 17 else (8000, 16)  # the forward needs F >= K lanes
+    n = B * F
+    rng = np.random.default_rng(17)
+    keys = rng.integers(0, 1 << 40, size=n).astype(np.int64)
+    keys[rng.random(n) < 0.25] = 12345  # ~32K occurrences of one key
+    r, d, uvals, y, g_at, g_b, g_s, ovf = _fm_three_reduces(dev, keys, B, F, dim, 17)
     assert int(ovf[0]) >= 1  # the hot key's bucket overflowed
     u = int(r.ucount[0])
+    _assert_fm_within_fp64_bound(f"fm overflow dim {dim}", r, uvals, y, B, F,
+                                 (("row atomics", g_at), ("LDS atomics", g_b),
+                                  ("sorted + overflow", g_s)))
     np.testing.assert_allclose(g_s[:u].cpu().numpy(), g_at[:u].cpu().numpy(), rtol=2e-3,
                                atol=5e-3)
+
+
+@pytest.mark.parametrize("total", [10240, 10241])
+def test_fm_sorted_reduce_bucket_boundary(dev, total):
+    """A bucket of exactly kFmOcc = 10240 occurrences is sorted in LDS, one of
+    10241 goes to the overflow list: both within the fp64 bound."""
+    from swiftsnails_amd._native import hip
+    from swiftsnails_amd.ops.dedup import Deduper
+
+    B, F, dim, hot = 16000, 8, 9, 12345
+    n = B * F
+    rng = np.random.default_rng(23)
+    keys = rng.integers(0, 1 << 40, size=n).astype(np.int64)
+    keys[0] = hot
+    # where the hot key's bucket is, and what else falls into it
+    d0 = Deduper(n, nranks=1, gdim=dim, device=dev, mode="bucket")
+    d0(torch.from_numpy(keys).to(dev))
+    torch.cuda.synchronize()
+    bkt = d0.bkt[:n].cpu().numpy()
+    others = int((bkt == bkt[0]).sum()) - 1
+    assert 0 < others < total - 1000
+    # more occurrences of the hot key, taken from other buckets, up to `total`
+    free = np.nonzero(bkt != bkt[0])[0]
+    keys[rng.choice(free, total - others - 1, replace=False)] = hot
+    r, d, uvals, y, g_at, g_b, g_s, ovf = _fm_three_reduces(dev, keys, B, F, dim, total)
+    P, o_bs, _, _ = hip().bd_offsets(d._lay(n), 1, d.ndest)
+    bstart = d.scratch[o_bs:o_bs + P + 1].cpu().numpy().astype(np.int64)
+    sizes = np.diff(bstart)
+    assert sizes.max() == total and (sizes > 10240).sum() == int(total > 10240)
+    assert int(ovf[0]) == int(total > 10240)
+    _assert_fm_within_fp64_bound(f"fm bucket of {total}", r, uvals, y, B, F,
+                                 (("row atomics", g_at), ("LDS atomics", g_b),
+                                  ("sorted lists", g_s)))
 
 
 def test_fm_trains_world1(dev):
