@@ -213,7 +213,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from _lr_oracle import B, EMPTY, ROWS, STEPS, U32, U_G, Dataset
+from _lr_oracle import B, EMPTY, ROWS, STEPS, U32, U_G, Dataset, update, update_bound
 
 F = {"fm_spread": 13, "fm_hot": 13, "fm_narrow": 6}
 KS = (1, 4, 8, 16)
@@ -468,20 +468,14 @@ class FMOracle:
         if mut == "per_occurrence":
             terms = np.concatenate([go[:, None], go[:, None] * (S[s] - vo)], axis=1)
             x, h = self._per_occurrence(x, h, inv, terms)
-        elif self.opt == "adagrad":
-            h = h + G * G
-            x = x - lr * G / np.sqrt(h + T(EPS))
         else:
-            x = x - lr * G
+            x, h = update(self.opt, self.lr, x, h, G, T)
         hs = np.roll(h, 1, axis=1) if mut == "h_shifted" else h  # h block one column off
         self.x[pos], self.h[pos] = x, hs
-        if self.opt == "adagrad":
-            den = np.sqrt(h.astype(np.float64) + EPS)
-            self.ill += int((eG > 0.1 * den).any(1).sum())
-            self.dx[pos] += self.lr * eG / den
-            self.dh[pos] += 2 * np.abs(G).astype(np.float64) * eG + eG * eG
-        else:
-            self.dx[pos] += self.lr * eG
+        dx, dh, ill = update_bound(self.opt, self.lr, h, G, eG)
+        self.ill += int(ill.any(1).sum())
+        self.dx[pos] += dx
+        self.dh[pos] += dh
         return loss
 
     def _per_occurrence(self, x, h, inv, terms):

@@ -172,6 +172,28 @@ def dataset(name: str) -> Dataset:
     return Dataset(name, keys, x, y, lines)
 
 
+# ----------------------------------------------------------------- update
+def update(opt: str, lr, x, h, G, T=np.float64):
+    """One optimizer step of every key (``ss/optim.h``), in ``T``: (x, h) after
+    it.  The one update of the LR, FM and word2vec oracles."""
+    lr = T(lr)
+    if opt == "adagrad":
+        h = h + G * G
+        return x - lr * G / np.sqrt(h + T(EPS)), h
+    return x - lr * G, h
+
+
+def update_bound(opt: str, lr, h_after, G, eG):
+    """(dx, dh, ill) of one step (module docstring): what a gradient known to
+    ``eG`` moves the parameters and the AdaGrad state by, and where the step
+    is ill-conditioned."""
+    if opt == "adagrad":
+        den = np.sqrt(np.asarray(h_after, np.float64) + EPS)
+        return (lr * eG / den, 2 * np.abs(np.asarray(G, np.float64)) * eG + eG * eG,
+                eG > 0.1 * den)
+    return lr * eG, np.zeros_like(eG), np.zeros(np.shape(eG), bool)
+
+
 # ------------------------------------------------------------------ model
 MUTANTS = ("x_one", "x_next", "drop_one", "dup_one", "per_occurrence")
 
@@ -275,19 +297,13 @@ class LROracle:
         lr, w, h = T(self.lr), self.w[pos], self.h[pos]
         if mut == "per_occurrence":
             w, h = self._per_occurrence(w, h, inv, term)
-        elif self.opt == "adagrad":
-            h = h + G * G
-            w = w - lr * G / np.sqrt(h + T(EPS))
         else:
-            w = w - lr * G
+            w, h = update(self.opt, self.lr, w, h, G, T)
         self.w[pos], self.h[pos] = w, h
-        if self.opt == "adagrad":
-            den = np.sqrt(h.astype(np.float64) + EPS)
-            self.ill += int((eG > 0.1 * den).sum())
-            self.dw[pos] += self.lr * eG / den
-            self.dh[pos] += 2 * np.abs(G) * eG + eG * eG
-        else:
-            self.dw[pos] += self.lr * eG
+        dw, dh, ill = update_bound(self.opt, self.lr, h, G, eG)
+        self.ill += int(ill.sum())
+        self.dw[pos] += dw
+        self.dh[pos] += dh
         return loss
 
     def _per_occurrence(self, w, h, inv, term):

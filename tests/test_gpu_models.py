@@ -57,6 +57,34 @@ def test_w2v_sgns_tile_matches_reference(dev, D, bf16):
         np.testing.assert_allclose(G[T + T * C + t * S:T + T * C + (t + 1) * S], gN, rtol=rt,
                                    atol=at)
     np.testing.assert_allclose(loss.sum().item(), tot, rtol=1e-4 if not bf16 else 3e-3)
+    # beside it, the derived bound: the fp32 tile against the exact fp64 model,
+    # the bf16 tile against fp64 arithmetic on the operands it rounds
+    import _w2v_oracle as O
+
+    o = O.grad_pairs(O.Spec("pairs", "shared", T, C // 2), U.astype(np.float64),
+                     "as_built" if bf16 else "exact", neg_scale=neg_scale)
+    _assert_w2v_within_bound(f"sgns tile D {D} bf16 {bf16}", G, o, loss.sum().item())
+
+
+def _assert_w2v_within_bound(label, G, o, loss):
+    """Every occurrence row within its derived bound (``_w2v_oracle.occ_bound``;
+    a row whose bound is zero is exactly zero), and the loss within its own.
+    No coordinate is widened: the score gradients the oracle flags as within
+    the fp32 error of a bf16 rounding midpoint are settled by decoding which
+    of them the kernel rounded the other way (``settle_occ``), and every
+    coordinate is held to that one candidate."""
+    import _w2v_oracle as O
+
+    ref, nflip = O.settle_occ(o, G)
+    tol = O.occ_bound(o)
+    err = np.abs(np.asarray(G, np.float64) - ref)
+    assert not err[tol == 0].any()
+    r = err / np.where(tol > 0, tol, 1.0)
+    # the loss: its own bound and the fp32 sum of the counter's shards
+    lr = abs(loss - o.loss) / (o.eloss + O.shard_sum_error(o.loss))
+    print(f"MARGIN {label}: max |kernel - oracle| / bound {r.max():.3f} ({nflip} of {o.flagged} "
+          f"flagged elements settled as flipped), loss {lr:.3f}")
+    assert r.max() <= 1 and lr <= 1, (label, float(r.max()), lr)
 
 
 @pytest.mark.parametrize("D,W,B", [(32, 2, 128), (64, 5, 150), (128, 5, 256), (128, 15, 100)])
@@ -113,10 +141,16 @@ def test_w2v_window_tile_matches_reference(dev, D, W, B):
     dead = ~mask.any(1)
     assert not G[:B][dead].any()
     assert not G[B:B + R][meta < 0].any()
+    # beside it, the derived bound against the as_built model (bf16 operands, fp64 arithmetic)
+    import _w2v_oracle as O
+
+    o = O.grad_window(O.Spec("window", "shared", B, W, 5), U.astype(np.float64), meta, "as_built")
+    assert o.pairs == npairs
+    _assert_w2v_within_bound(f"window tile D {D} W {W} B {B}", G, o, loss.sum().item())
 
 
 @pytest.mark.parametrize("D,W,K,B", [(32, 2, 3, 70), (64, 5, 5, 128), (128, 5, 5, 200),
-                                     (128, 15, 16, 40)])
+                                     (128, 15, 16, 40), (64, 5, 6, 70), (32, 3, 11, 70)])
 def test_w2v_per_pair_negatives_match_reference(dev, D, W, K, B):
     """Classic SGNS (k_w2v_pp + k_w2v_ppctx): K negatives per positive pair,
     gradients as occurrence rows.  The center rows and the run-position rows
@@ -171,6 +205,14 @@ def test_w2v_per_pair_negatives_match_reference(dev, D, W, K, B):
     assert mask.sum() > 0 and pairs.sum().item() == mask.sum()
     np.testing.assert_allclose(G, ref, rtol=2e-4, atol=2e-5)
     np.testing.assert_allclose(loss.sum().item(), l, rtol=1e-4)
+    # beside it, the derived bound against the exact fp64 model (k_w2v_pp for
+    # K <= 5, k_w2v_pp16 from K = 6, k_w2v_ppctx; the negatives' rows are
+    # expanded above in fp64, inside the bound's product rounding)
+    import _w2v_oracle as O
+
+    o = O.grad_per_pair(O.Spec("window", "per_pair", B, W, K), U.astype(np.float64), meta)
+    assert o.pairs == mask.sum()
+    _assert_w2v_within_bound(f"per-pair D {D} W {W} K {K} B {B}", G, o, loss.sum().item())
 
 
 def test_w2v_stream_gen_window_layout(dev):
@@ -1098,3 +1140,158 @@ def test_w2v_fused_update_matches_apply(dev, monkeypatch, neg_mode, opt):
         close = np.isclose(a, b, rtol=1e-4, atol=1e-7)
         assert close.mean() > 0.999, (close.size - close.sum(), close.size)
         assert np.abs(a - b).max() <= 2 * lr + 1e-3
+
+
+def _osort_inputs(dev, keys):
+    """A bucket ``Deduper`` over ``keys`` and ``k_w2v_osort`` on its layout:
+    (deduper, uid of every key position, items [n, 4], ord [n], uhot [n])."""
+    from swiftsnails_amd._native import hip
+    from swiftsnails_amd.ops.dedup import Deduper
+
+    n = len(keys)
+    dd = Deduper(n, device=dev, mode="bucket", with_grad=False)
+    dd(torch.from_numpy(keys.view(np.int64)).to(dev))
+    _, bstart, unum, ubase, P = dd.bucket_view(n)
+    assert P >= 3
+    order = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    items = torch.full((n, 4), -1, dtype=torch.int32, device=dev)
+    uhot = torch.full((n,), 7, dtype=torch.uint8, device=dev)
+    hip().w2v_osort(P, bstart, unum, ubase, dd.pj.data_ptr(), dd.luid.data_ptr(),
+                    order.data_ptr(), items.data_ptr(), torch.cuda.current_stream().cuda_stream,
+                    uhot.data_ptr())
+    torch.cuda.synchronize()
+    dd.check()
+    uid = dd.unique_ids(n).cpu().numpy()
+    return dd, uid, items, order, uhot
+
+
+def _check_osort(keys, uid, items, order, uhot):
+    """``items`` / ``ord`` / ``uhot`` against the keys alone; returns each
+    key position's item index."""
+    n = len(keys)
+    it, od, uh = items.cpu().numpy().view(np.uint32), order.cpu().numpy(), uhot.cpu().numpy()
+    u, inv, cnt = np.unique(keys, return_inverse=True, return_counts=True)
+    assert (uid >= 0).all() and len(np.unique(uid)) == len(u)
+    first = np.zeros(len(u), np.int64)
+    first[inv] = uid                      # one uid per key
+    assert np.array_equal(first[inv], uid)
+    live = it[:, 1] > 0
+    assert not it[~live].any()            # the unused item slots are zero
+    assert it[live, 1].max() <= 32        # no item exceeds 32 occurrences
+    seen = np.zeros(n, np.int64)
+    item_of = np.full(n, -1, np.int64)
+    nit = np.zeros(len(u), np.int64)
+    for s in np.nonzero(live)[0]:
+        x, c, z, f = (int(v) for v in it[s])
+        pos = np.array([x]) if f & 2 else od[x:x + c]
+        assert (uid[pos] == z).all()      # an item holds one key's occurrences
+        k = inv[pos[0]]
+        seen[pos] += 1
+        item_of[pos] = s
+        nit[k] += 1
+        # flag 2: exactly the single occurrences, the item carrying the position itself
+        assert bool(f & 2) == (cnt[k] == 1) and (not f & 2 or c == 1)
+        assert bool(f & 1) == (cnt[k] > 32)                            # flag 1: several items
+    assert (seen == 1).all()              # every occurrence position in exactly one item
+    assert np.array_equal(nit, -(-cnt // 32))
+    assert np.array_equal(uh[first].astype(bool), cnt > 32)   # uhot exactly on those keys
+    return item_of
+
+
+def _w2v_reduce_body(D, form):
+    """``k_w2v_oreduce`` (window form, or the scaled per-pair form of this
+    process's ``SS_W2V_PP_ITEMS``) on random rows against ``np.add.at`` in
+    fp64, within ``n 2^-24 sum |row|`` per coordinate."""
+    import _w2v_oracle as O
+    from swiftsnails_amd._native import hip
+
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    rng = np.random.default_rng(D)
+    window = form == "window"
+    d = O.data("w2v_win" if window else "w2v_pp/w5k5")
+    sp, B, W, R = d.sp, d.sp.B, d.sp.W, d.sp.R
+    for t in (0, 1):   # even steps: counts 1 .. 65; odd steps: the 300-occurrence key too
+        keys = d.keys[t]
+        n = len(keys)
+        assert {1, 2, 31, 32, 33} <= set(d.plan[t]) and (t == 0 or O.HOT in d.plan[t])
+        dd, uid, items, order, uhot = _osort_inputs(dev, keys)
+        _check_osort(keys, uid, items, order, uhot)
+        nu = int(uid.max()) + 1
+        rows = n if window else B + R
+        og = (rng.standard_normal((rows, D)) * 0.5).astype(np.float32)
+        ntail = max(1, (sp.tiles - 1) * 2 * W)
+        ot = (rng.standard_normal((ntail, D)) * 0.5).astype(np.float32)
+        acc = rng.standard_normal(2 * 64).astype(np.float32)
+        t_og, t_ot, t_acc = (torch.from_numpy(a).to(dev) for a in (og, ot, acc))
+        t_out = torch.full_like(t_acc, 3.0)
+        ug = torch.zeros((n, D), device=dev)   # (a several-item key's row atomics add into zeros)
+        ref, mag, terms = np.zeros((nu, D)), np.zeros((nu, D)), np.zeros(nu)
+        np.add.at(ref, uid[:rows], og.astype(np.float64))
+        np.add.at(mag, uid[:rows], np.abs(og).astype(np.float64))
+        np.add.at(terms, uid, 1)
+        st = torch.cuda.current_stream().cuda_stream
+        if window:
+            q = np.arange(R)
+            tail = (q >= 64) & (q % 64 < 2 * W) & (q // 64 <= sp.tiles - 1)
+            tq = (q // 64 - 1) * 2 * W + q % 64
+            assert tail.sum() == ntail and sorted(tq[tail]) == list(range(ntail))
+            np.add.at(ref, uid[B + q[tail]], ot[tq[tail]].astype(np.float64))
+            np.add.at(mag, uid[B + q[tail]], np.abs(ot[tq[tail]]).astype(np.float64))
+            np.add.at(terms, uid[B + q[tail]], 1)
+            hip().w2v_oreduce(items.data_ptr(), n, order.data_ptr(), t_og.data_ptr(),
+                              t_ot.data_ptr(), B, W, D, ug.data_ptr(), st, acc=t_acc.data_ptr(),
+                              acc_out=t_out.data_ptr(), acc_n=t_acc.numel())
+        else:
+            uv = (rng.standard_normal((nu, D)) * 0.5).astype(np.float32)
+            nneg = n - rows
+            gn = rng.random(nneg).astype(np.float32)
+            cen = uid[rng.integers(0, B, nneg)].astype(np.uint32)
+            dead = rng.random(nneg) < 0.1           # negatives of pairs that are not valid
+            gn[dead], cen[dead] = 0.0, 0xFFFFFFFF
+            gnc = np.stack([gn, cen.view(np.float32)], 1)
+            live = ~dead
+            term = gn[live, None].astype(np.float64) * uv[cen[live].astype(np.int64)]
+            np.add.at(ref, uid[rows:][live], term)
+            np.add.at(mag, uid[rows:][live], np.abs(term))
+            t_uv, t_gnc = torch.from_numpy(uv).to(dev), torch.from_numpy(gnc).to(dev)
+            hip().w2v_oreduce(items.data_ptr(), n, order.data_ptr(), t_og.data_ptr(), 0, B, W, D,
+                              ug.data_ptr(), st, gnc=t_gnc.data_ptr(), negbase=rows,
+                              uvals=t_uv.data_ptr(), acc=t_acc.data_ptr(),
+                              acc_out=t_out.data_ptr(), acc_n=t_acc.numel())
+        torch.cuda.synchronize()
+        # the accumulator hand-off is exact: moved, and left zero
+        assert np.array_equal(t_out.cpu().numpy(), acc) and not t_acc.cpu().numpy().any()
+        got = ug.cpu().numpy()[:nu].astype(np.float64)
+        assert not ug.cpu().numpy()[nu:].any()
+        tol = (terms + 1)[:, None] * 2.0 ** -24 * mag
+        err = np.abs(got - ref)
+        assert not err[tol == 0].any()
+        r = (err / np.where(tol > 0, tol, 1.0)).max()
+        print(f"MARGIN oreduce {form} D {D} step {t} PP_ITEMS "
+              f"{os.environ.get('SS_W2V_PP_ITEMS', '2')}: max |kernel - fp64| / bound {r:.3f}")
+        assert r <= 1, (form, D, t, r)
+
+
+def _w2v_reduce_child(dims, form, items):
+    os.environ["SS_W2V_PP_ITEMS"] = items   # read at the first launch of this process
+    for D in dims:
+        _w2v_reduce_body(D, form)
+
+
+@pytest.mark.parametrize("D", [32, 64, 128])
+@pytest.mark.parametrize("form", ["window", "per_pair"])
+def test_w2v_osort_oreduce_match_fp64_sums(dev, monkeypatch, D, form):
+    """The sort and the reduce alone: ``k_w2v_osort``'s items / ord / uhot
+    checked against the keys (occurrence counts 1, 2, 31, 32, 33, 64, 65 and
+    300 over several buckets, tail rows at B = 200, W = 5), then
+    ``k_w2v_oreduce`` (window form) and ``k_w2v_oreduce_pp2`` (the per-pair
+    form's default) against fp64 sums."""
+    monkeypatch.delenv("SS_W2V_PP_ITEMS", raising=False)
+    _w2v_reduce_body(D, form)
+
+
+def test_w2v_oreduce_scaled_one_item_per_half_wave():
+    """``k_w2v_oreduce<D, true>`` at D 32 / 64 / 128 (``SS_W2V_PP_ITEMS=1``,
+    read once per process: a child of its own)."""
+    in_child(_w2v_reduce_child, (32, 64, 128), "per_pair", "1", always=True)
