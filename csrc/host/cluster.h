@@ -79,8 +79,17 @@ inline InitParams init_from_config(const ConfigParser& c) {
 }
 inline OptParams opt_from_config(const ConfigParser& c) {
   const std::string k = c.get("optimizer", "sgd");
+  // Adam's bias corrections belong to the round being applied.  This server
+  // applies each worker's push on its own handler thread under the shard
+  // locks alone: it has no round and no one place to count one, and with
+  // bc1 = bc2 = 1 its first steps would be about 3.2 lr.  The Python servers
+  // (HbmTable / HostTable behind the engine) count rounds and implement it.
+  if (k == "adam")
+    throw Error("optimizer: adam is not implemented by the native C++ cluster server (it keeps no "
+                "round count for the bias corrections); the Python servers implement it "
+                "(swiftsnails_amd HbmTable / HostTable behind PSEngine)");
   OptParams op{};
-  op.kind = k == "adagrad" ? kOptAdaGrad : k == "ftrl" ? kOptFTRL : k == "adam" ? kOptAdam : kOptSGD;
+  op.kind = k == "adagrad" ? kOptAdaGrad : k == "ftrl" ? kOptFTRL : kOptSGD;
   op.lr = std::stof(c.get("learning_rate", "0.01"));
   op.l1 = std::stof(c.get("l1", "0"));
   op.l2 = std::stof(c.get("l2", "0"));

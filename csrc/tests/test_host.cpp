@@ -402,6 +402,30 @@ TEST(cluster_master_servers_workers_inprocess) {
   std::remove(dump.c_str());
 }
 
+// The native server keeps no round count, so it cannot form Adam's bias
+// corrections: the config key is refused, and the message names the servers
+// that implement the rule.  The other three rules are accepted.
+TEST(cluster_refuses_adam_and_names_the_python_servers) {
+  ConfigParser c;
+  c.parse_string("optimizer: adam\nlearning_rate: 0.1\n");
+  std::string what;
+  try {
+    opt_from_config(c);
+  } catch (const std::exception& e) {
+    what = e.what();
+  }
+  EXPECT(what.find("adam") != std::string::npos);
+  EXPECT(what.find("Python servers") != std::string::npos);
+  const char* names[] = {"sgd", "adagrad", "ftrl"};
+  const int kinds[] = {kOptSGD, kOptAdaGrad, kOptFTRL};
+  for (int i = 0; i < 3; ++i) {
+    ConfigParser k;
+    k.parse_string(std::string("optimizer: ") + names[i] + "\n");
+    const OptParams op = opt_from_config(k);
+    EXPECT(op.kind == kinds[i] && op.bc1 == 1.f && op.bc2 == 1.f);
+  }
+}
+
 // ---------------------------------------------------------------- data input
 TEST(sparse_dataset_parse_and_fill) {
   const std::string p = tmpfile("a.svm", "1 3:0.5 7\n0 9:2\n-1\n1 1 2 3 4 5 6\n");

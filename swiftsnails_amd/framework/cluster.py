@@ -170,6 +170,7 @@ class _LocalClient:
 
     def push(self, keys, grads):
         self.table.push_keys(keys.view(np.int64), grads.reshape(len(keys), -1))
+        self.table.next_round()  # one in-process worker: every push is a round (Adam's t)
 
 
 class SwiftWorker:

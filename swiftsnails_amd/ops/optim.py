@@ -72,10 +72,17 @@ class Optimizer:
         return state_width(self.kind, dim)
 
     def bias_corrections(self):
+        """Adam's ``1 / (1 - beta^t)`` for the round being applied.  ``step``
+        counts the rounds already applied (``next_round`` runs after a
+        round's pushes; checkpoints store it as ``opt_step``), so that round
+        is ``t = step + 1``.  The betas are taken as the fp32 numbers the
+        kernels multiply by: from the decimal ``0.999`` the correction would
+        miss the kernels' ``1 - beta2`` by 1.3e-5 relative."""
         if self.kind != "adam":
             return 1.0, 1.0
-        t = max(1, self.step)
-        return 1.0 / (1.0 - self.beta1**t), 1.0 / (1.0 - self.beta2**t)
+        t = self.step + 1
+        b1, b2 = float(np.float32(self.beta1)), float(np.float32(self.beta2))
+        return 1.0 / (1.0 - b1**t), 1.0 / (1.0 - b2**t)
 
     def native(self):
         from .._native import hip

@@ -30,6 +30,10 @@ The model (``LROracle``), per step over the batch's non-EMPTY entries
     sgd:      w_k -= lr * G_k
 once per key and step; a key seen for the first time starts from
 ``init_reference`` (uniform, scale 0.01; h = 0).
+FTRL-Proximal, lazy Adam and the regularised settings (L1 / L2, clip, scale)
+step by ``_opt_oracle.step`` instead, on fp32 hyperparameters, the gradient
+entering it known to eG and the bound it carries taking the place of the
+dw / dh sums below (``OPT_SETTINGS``; ``test_gpu_opt_oracle.py``).
 
 The error bound carried beside the state
 ----------------------------------------
@@ -93,12 +97,14 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+import _opt_oracle as _opt
+
 EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
 B, F, STEPS = 4096, 13, 8
 ROWS = B * STEPS
 U32 = 2.0 ** -24   # fp32 unit round-off
 U_G = 2.0 ** -21   # relative accuracy of one gradient term (module docstring)
-LR = {"adagrad": 0.05, "sgd": 1e-3}
+LR = {"adagrad": 0.05, "sgd": 1e-3, "ftrl": 0.05, "adam": 0.01}   # (FTRL steps by ftrl_alpha)
 INIT_SCALE, EPS = 0.01, 1e-8
 SEEDS = {"binary32": 0, "valued64": 1}
 
@@ -173,14 +179,17 @@ def dataset(name: str) -> Dataset:
 
 
 # ----------------------------------------------------------------- update
-def update(opt: str, lr, x, h, G, T=np.float64):
-    """One optimizer step of every key (``ss/optim.h``), in ``T``: (x, h) after
-    it.  The one update of the LR, FM and word2vec oracles."""
-    lr = T(lr)
-    if opt == "adagrad":
-        h = h + G * G
-        return x - lr * G / np.sqrt(h + T(EPS)), h
-    return x - lr * G, h
+def update(opt: str, lr, x, h, G, T=np.float64, h2=None, t: int = 1, **reg):
+    """One optimizer step of every key, in ``T``: (x, h) after it — the one
+    update of the LR, FM and word2vec oracles — by the rules of
+    ``_opt_oracle.py``.  FTRL and Adam have a second state ``h2`` and return
+    (x, h, h2); ``t`` is Adam's 1-based round; ``reg``: ``l1``, ``l2``,
+    ``grad_scale``, ``clip`` and the rules' other hyperparameters."""
+    hy = _opt.Hyper(opt, lr=lr, eps=EPS, **reg)
+    w, s1, s2 = _opt.step(hy, x, h if opt != "sgd" else None, h2, G, t, T, track=False)
+    if opt in ("sgd", "adagrad"):
+        return w.v, (h if s1 is None else s1.v)
+    return w.v, s1.v, s2.v
 
 
 def update_bound(opt: str, lr, h_after, G, eG):
@@ -202,12 +211,14 @@ MUTANTS = ("x_one", "x_next", "drop_one", "dup_one", "per_occurrence")
 class Result:
     keys: np.ndarray    # sorted, distinct
     w: np.ndarray
-    h: np.ndarray       # zeros with sgd
+    h: np.ndarray       # zeros with sgd; FTRL's z, Adam's m
     tol_w: np.ndarray
     tol_h: np.ndarray
     losses: list        # per step: per-sample losses (fp64)
     ill: int            # ill-conditioned key-steps
     zmax: float
+    h2: np.ndarray = None      # FTRL's n, Adam's v
+    tol_h2: np.ndarray = None
 
     def mean_losses(self, world: int = 1) -> np.ndarray:
         """[steps, world]: each rank's mean loss (the batch is the ranks'
@@ -223,11 +234,19 @@ class LROracle:
     wrong."""
 
     def __init__(self, optimizer: str = "adagrad", lr: float | None = None, dtype=np.float64,
-                 perm: int | None = None, mutant: str | None = None):
+                 perm: int | None = None, mutant: str | None = None, **reg):
         from swiftsnails_amd.ops.optim import InitConfig
 
         assert optimizer in LR and mutant in (None,) + MUTANTS
         self.opt, self.lr = optimizer, LR[optimizer] if lr is None else lr
+        # FTRL, Adam and the regularised settings (``reg``: l1, l2, clip,
+        # grad_scale, ...) step by ``_opt_oracle.step`` on fp32 hyperparameters
+        # and carry its running bound (the gradient enters it known to eG);
+        # plain AdaGrad and SGD keep ``update`` / ``update_bound``
+        self.general = optimizer in ("ftrl", "adam") or bool(reg)
+        self.hy = _opt.Hyper(optimizer, lr=self.lr, eps=EPS, **reg).f32()
+        self.t = 0
+        self.h2, self.dh2 = np.empty(0, dtype), np.empty(0)
         self.T, self.mutant = dtype, mutant
         self.rng = np.random.default_rng(perm) if perm is not None else None
         self.init = InitConfig("uniform", INIT_SCALE)
@@ -255,6 +274,8 @@ class LROracle:
             self.h = np.concatenate([self.h, r[:, 1].astype(self.T)])[order]
             self.dw = np.concatenate([self.dw, z])[order]
             self.dh = np.concatenate([self.dh, z])[order]
+            self.h2 = np.concatenate([self.h2, z.astype(self.T)])[order]
+            self.dh2 = np.concatenate([self.dh2, z])[order]
             pos = np.searchsorted(self.keys, u)
         return pos
 
@@ -295,6 +316,8 @@ class LROracle:
         eG = U_G * A + U32 * cnt + cnt * U32 * A
         # the update, once per key
         lr, w, h = T(self.lr), self.w[pos], self.h[pos]
+        if self.general:
+            return self._general_step(pos, G, eG, loss)
         if mut == "per_occurrence":
             w, h = self._per_occurrence(w, h, inv, term)
         else:
@@ -304,6 +327,25 @@ class LROracle:
         self.ill += int(ill.sum())
         self.dw[pos] += dw
         self.dh[pos] += dh
+        return loss
+
+    def _general_step(self, pos, G, eG, loss):
+        """One round of ``_opt_oracle.step`` per key: the states go in with
+        the bound they carry, the gradient with eG, and come out with both
+        propagated (``dw`` / ``dh`` / ``dh2`` hold the running bound itself)."""
+        ns = _opt.NSTATE[self.opt]
+        self.t += 1
+        w, s1, s2 = _opt.step(
+            self.hy, _opt.N(self.w[pos], self.dw[pos]),
+            _opt.N(self.h[pos], self.dh[pos]) if ns > 0 else None,
+            _opt.N(self.h2[pos], self.dh2[pos]) if ns > 1 else None,
+            _opt.N(G, eG), self.t, self.T)
+        self.w[pos], self.dw[pos] = w.v, w.e
+        if ns > 0:
+            self.h[pos], self.dh[pos] = s1.v, s1.e
+        if ns > 1:
+            self.h2[pos], self.dh2[pos] = s2.v, s2.e
+        self.ill += int((~np.isfinite(w.e)).sum())
         return loss
 
     def _per_occurrence(self, w, h, inv, term):
@@ -326,6 +368,11 @@ class LROracle:
 
     def result(self) -> Result:
         w, h = self.w.astype(np.float64), self.h.astype(np.float64)
+        if self.general:
+            h2, S = self.h2.astype(np.float64), _opt.SAFETY
+            return Result(self.keys.copy(), w, h, 1e-6 + 1e-4 * np.abs(w) + S * self.dw,
+                          1e-7 + 1e-4 * np.abs(h) + S * self.dh, self.losses, self.ill, self.zmax,
+                          h2, 1e-7 + 1e-4 * np.abs(h2) + S * self.dh2)
         return Result(self.keys.copy(), w, h, 1e-6 + 1e-4 * np.abs(w) + self.dw,
                       1e-7 + 1e-4 * h + self.dh, self.losses, self.ill, self.zmax)
 
@@ -341,30 +388,60 @@ def batches(name: str, world: int = 1, steps: int = STEPS):
     return out
 
 
-def run(name: str, optimizer: str, world: int = 1, **kw) -> Result:
+def run(name: str, optimizer: str, world: int = 1, steps: int = STEPS, **kw) -> Result:
     orc = LROracle(optimizer, **kw)
-    for k, x, y in batches(name, world):
+    for k, x, y in batches(name, world, steps):
         orc.step(k, x, y)
     return orc.result()
 
 
 @functools.lru_cache(maxsize=None)
-def reference(name: str, optimizer: str, world: int = 1) -> Result:
-    """The fp64 reference of a data set and optimizer, computed once and
-    shared (read-only) by every test that needs it."""
-    r = run(name, optimizer, world)
-    for a in (r.keys, r.w, r.h, r.tol_w, r.tol_h):
-        a.setflags(write=False)
+def reference(name: str, optimizer: str, world: int = 1, steps: int = STEPS,
+              reg: tuple = ()) -> Result:
+    """The fp64 reference of a data set and optimizer (``reg``: the
+    regularisation as sorted (name, value) pairs), computed once and shared
+    (read-only) by every test that needs it."""
+    r = run(name, optimizer, world, steps, **dict(reg))
+    for a in (r.keys, r.w, r.h, r.tol_w, r.tol_h, r.h2, r.tol_h2):
+        if a is not None:
+            a.setflags(write=False)
     return r
 
 
-def ratios(res: Result, keys: np.ndarray, w: np.ndarray, h: np.ndarray | None = None):
+# The rule settings the engine is held to (test_gpu_opt_oracle.py): rule and
+# regularisation as ``reference``'s ``reg``; 4 steps each.
+OPT_STEPS = 4
+OPT_SETTINGS = {
+    "ftrl_l1": ("ftrl", (("l1", 0.3),)),
+    "adam": ("adam", ()),
+    "adagrad_l2_clip": ("adagrad", (("clip", 1.0), ("l2", 0.01))),
+    "sgd_l2": ("sgd", (("l2", 0.01),)),
+}
+
+
+def opt_reference(tag: str, name: str, world: int = 1) -> Result:
+    opt, reg = OPT_SETTINGS[tag]
+    return reference(name, opt, world, OPT_STEPS, reg)
+
+
+def ftrl_near_threshold(res: Result, l1: float) -> np.ndarray:
+    """Keys whose ``|z| - l1`` lies inside z's tolerance: the only keys whose
+    ``w == 0`` may differ from the oracle's."""
+    return np.abs(np.abs(res.h) - np.float64(np.float32(l1))) <= res.tol_h
+
+
+def ratios(res: Result, keys: np.ndarray, w: np.ndarray, h: np.ndarray | None = None,
+           h2: np.ndarray | None = None):
     """(max |w - ref| / tol_w, max |h - ref| / tol_h, share of keys outside
-    either) of a model over exactly ``res.keys`` (any order, each once)."""
+    either) of a model over exactly ``res.keys`` (any order, each once);
+    ``h2``: the second state is held to ``tol_h2`` too, its ratio folded into
+    the second figure."""
     order = np.argsort(keys)
     keys = keys[order]
     assert len(keys) == len(res.keys) and np.array_equal(keys, res.keys), (len(keys), len(res.keys))
     rw = np.abs(w[order].astype(np.float64) - res.w) / res.tol_w
     rh = (np.abs(h[order].astype(np.float64) - res.h) / res.tol_h if h is not None
           else np.zeros_like(rw))
+    if h2 is not None:
+        rh = np.maximum(rh, np.abs(h2[order].astype(np.float64) - res.h2) / res.tol_h2)
     return float(rw.max()), float(rh.max()), float(((rw > 1) | (rh > 1)).mean())
