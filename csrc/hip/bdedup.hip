@@ -940,7 +940,9 @@ __global__ __launch_bounds__(RT) void k_bd_reduce(const uint32_t* __restrict__ b
   }
   __syncthreads();
   if (slots || slots32) {
-    // fused K5 (scalar AdaGrad rows): the merged gradient goes straight into
+    // fused K5 (scalar two-float rows: AdaGrad's (w, h), FTRL's (z, n); op.kind
+    // is a kernel argument, the rule's switch a uniform branch): the merged
+    // gradient goes straight into
     // the optimizer update — from the (w, h) the pull snapshot (coalesced,
     // then one blind 8-byte store per key), or read from the row when no
     // snapshot is valid (N>1 servers with pull-ahead: a read-modify-write).
@@ -1690,6 +1692,12 @@ void launch_bd_unplace(long long n, int nranks, const uint32_t* scratch, const f
   check_launch("k_bd_unplace");
 }
 
+// the rules whose scalar row is a two-float pair the fused merge updates:
+// AdaGrad's (w, h) and, on a table of [z | n] rows, FTRL's (z, n)
+static bool scalar_pair_rule(int kind, const DevTable& t) {
+  return (kind == kOptAdaGrad && !t.zn) || (kind == kOptFTRLzn && t.zn);
+}
+
 void launch_bd_reduce(long long n, int nranks, const uint32_t* scratch, const uint32_t* pj,
                       const uint32_t* luid, const float* gs, const float* xval, int F,
                       float* ugrad, hipStream_t st, int osi, const uint8_t* usingle,
@@ -1705,9 +1713,9 @@ void launch_bd_reduce(long long n, int nranks, const uint32_t* scratch, const ui
   DevTable tv{};
   OptParams opv{};
   if (slots || s32) {
-    if (!t || !op || osi || t->bf16 || op->kind != kOptAdaGrad || t->dim != 1 || t->width != 2 ||
-        t->row_off % 8 != 0 || t->stride % 8 != 0)
-      throw_error("bd_reduce: fused apply needs scalar AdaGrad rows and compact ids");
+    if (!t || !op || osi || t->bf16 || !scalar_pair_rule(op->kind, *t) || t->dim != 1 ||
+        t->width != 2 || t->row_off % 8 != 0 || t->stride % 8 != 0)
+      throw_error("bd_reduce: fused apply needs scalar AdaGrad or FTRL (z, n) rows and compact ids");
     tv = *t;
     opv = *op;
   }
@@ -1735,9 +1743,9 @@ void launch_bd_reduce_p(int P, const uint32_t* bstart, const uint32_t* ubase, co
   const int* s32 = slot32 ? reinterpret_cast<const int*>(slots) : nullptr;
   if (slot32) slots = nullptr;
   if (slots || s32) {
-    if (!t || !op || t->bf16 || op->kind != kOptAdaGrad || t->dim != 1 || t->width != 2 ||
-        t->row_off % 8 != 0 || t->stride % 8 != 0)
-      throw_error("bd_reduce_p: fused apply needs scalar AdaGrad rows");
+    if (!t || !op || t->bf16 || !scalar_pair_rule(op->kind, *t) || t->dim != 1 ||
+        t->width != 2 || t->row_off % 8 != 0 || t->stride % 8 != 0)
+      throw_error("bd_reduce_p: fused apply needs scalar AdaGrad or FTRL (z, n) rows");
     tv = *t;
     opv = *op;
   }

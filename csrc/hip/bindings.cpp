@@ -68,19 +68,26 @@ PYBIND11_MODULE(_ss_hip, m) {
   py::class_<DevTable>(m, "DevTable", py::module_local())
       .def(py::init([](uintptr_t base, unsigned long long cap, uint32_t stride, uint32_t key_off,
                        uint32_t dim, uint32_t width, uint32_t prefilled, uint32_t row_off,
-                       uint32_t bf16, uint32_t rbits) {
+                       uint32_t bf16, uint32_t rbits, uint32_t zn, float l1, float l2,
+                       float alpha, float beta) {
              const uint32_t eb = bf16 ? 2u : 4u;
+             if (zn && (bf16 || dim != 1 || width != 2 || row_off % 8 != 0 || stride % 8 != 0))
+               throw std::invalid_argument("DevTable: [z | n] rows are scalar fp32 pairs, 8-byte "
+                                           "aligned");
              if (row_off + eb * width > stride || (key_off < row_off + eb * width && key_off + 8 > row_off))
                throw std::invalid_argument("DevTable: row and key overlap inside the slot");
              // region tables: 2^rbits equal regions of >= 64 slots
              if (rbits > 20 || (rbits && (cap % (1ull << rbits) != 0 || (cap >> rbits) < 64)))
                throw std::invalid_argument("DevTable: rbits needs cap = rlen * 2^rbits, rlen >= 64");
              return DevTable{P<char>(base), cap, stride, key_off, dim, width, prefilled, row_off,
-                             bf16, rbits, rbits ? (cap >> rbits) : cap};
+                             bf16, rbits, rbits ? (cap >> rbits) : cap, zn ? 1u : 0u, l1, l2,
+                             alpha, beta};
            }),
            py::arg("base"), py::arg("cap"), py::arg("stride"), py::arg("key_off"), py::arg("dim"),
            py::arg("width"), py::arg("prefilled") = 0, py::arg("row_off") = 0,
-           py::arg("bf16") = 0, py::arg("rbits") = 0)
+           py::arg("bf16") = 0, py::arg("rbits") = 0, py::arg("zn") = 0, py::arg("l1") = 0.f,
+           py::arg("l2") = 0.f, py::arg("alpha") = 0.05f, py::arg("beta") = 1.f)
+      .def_readonly("zn", &DevTable::zn)
       .def_readonly("rbits", &DevTable::rbits)
       .def_readonly("rlen", &DevTable::rlen)
       .def_readonly("bf16", &DevTable::bf16)
@@ -430,13 +437,17 @@ PYBIND11_MODULE(_ss_hip, m) {
   m.def("srv_merge", [](int Pn, uintptr_t bstart, uintptr_t ubase, uintptr_t unum, uintptr_t pj,
                         uintptr_t luid, uintptr_t grads, uintptr_t merged, int D,
                         std::optional<DevTable> t, uintptr_t slots, uintptr_t snap,
-                        std::optional<OptParams> op, uintptr_t st) {
+                        std::optional<OptParams> op, uintptr_t st, int slot32, uintptr_t bkeys) {
+    // slot32 / bkeys (scalar rows): 4-byte slot indices, and whole
+    // [row | key] 16-byte slot stores with the buckets' staged keys
+    if (D != 1 && (slot32 || bkeys))
+      throw std::invalid_argument("srv_merge: slot32 / bkeys are for scalar rows");
     if (D == 1)
       launch_bd_reduce_p(Pn, P<const uint32_t>(bstart), P<const uint32_t>(ubase),
                          P<const uint32_t>(unum), P<const uint32_t>(pj), P<const uint32_t>(luid),
                          P<const float>(grads), 1, P<float>(merged), t ? &*t : nullptr,
                          P<const long long>(slots), P<const float>(snap), op ? &*op : nullptr,
-                         S(st));
+                         S(st), SelfSeg{}, slot32, P<const uint64_t>(bkeys));
     else
       launch_srv_merge_rows(Pn, P<const uint32_t>(bstart), P<const uint32_t>(ubase),
                             P<const uint32_t>(unum), P<const uint32_t>(pj),
@@ -446,7 +457,8 @@ PYBIND11_MODULE(_ss_hip, m) {
   }, py::arg("P"), py::arg("bstart"), py::arg("ubase"), py::arg("unum"), py::arg("pj"),
      py::arg("luid"), py::arg("grads"), py::arg("merged"), py::arg("D"),
      py::arg("t") = std::nullopt, py::arg("slots") = 0, py::arg("snap") = 0,
-     py::arg("op") = std::nullopt, py::arg("st") = 0);
+     py::arg("op") = std::nullopt, py::arg("st") = 0, py::arg("slot32") = 0,
+     py::arg("bkeys") = 0);
   m.def("fm_fwd_g", [](uintptr_t inv, std::vector<uintptr_t> ix, uintptr_t labels, int B,
                        int F, int dim, uintptr_t uvals, uintptr_t gs, uintptr_t gss,
                        uintptr_t loss, uintptr_t pred, uintptr_t st) {

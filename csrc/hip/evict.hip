@@ -80,8 +80,12 @@ __global__ __launch_bounds__(256) void k_evict_mark(DevTable t, EvictRule rule, 
       if (!rhas[r]) rhas[r] = 1;
     } else {
       const bool v = mask ? mask[s] != 0
-                          : evict_victim(rule, t.dim, acc_off,
-                                         [&](uint32_t j) { return row_ld(t, s, j); });
+                          : evict_victim(rule, t.dim, acc_off, [&](uint32_t j) {
+                              // [z | n] rows: w_below reads the derived weight
+                              return t.zn && j < t.dim
+                                         ? pull_val(t, row_ld(t, s, 0), row_ld(t, s, 1))
+                                         : row_ld(t, s, j);
+                            });
       f = kEvOcc | (v ? kEvVictim : 0);
       nv += v;
     }

@@ -368,7 +368,7 @@ class RoundEngine {
   // N>1: gradient rows into the servers' mailboxes, wait for every source's,
   // server merge per distinct key, then the slot-free event.  `update`, how a
   // shard's merge applies the optimizer (PSEngine._server_update_kind):
-  // "scalar" — fused with the AdaGrad update of scalar rows (`snap`: from the
+  // "scalar" — fused with the update of scalar two-float rows (`snap`: from the
   // pull's snapshot, else from the row); "rows" — fused into the update of
   // wider rows; absent — merged rows only (into sgrad): the caller applies
   // them (the apply kernel, or a tensor-code rule) and releases the slot.

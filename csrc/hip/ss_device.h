@@ -6,7 +6,8 @@
 //   * one open-addressed table per GPU shard, array-of-slots layout:
 //       slot = [ row: `width` fp32 (params then optimizer state) | pad | key u64 ]
 //     so a lookup-or-init + row gather touches the same cache line(s): for
-//     sparse LR (width 2: w, adagrad-acc) a slot is exactly 16 B and one random
+//     sparse LR (width 2: AdaGrad's w, h or FTRL's z, n — kOptFTRLzn, whose
+//     pulled w is derived, pull_val) a slot is exactly 16 B and one random
 //     HBM access serves probe + gather + update.
 //   * linear probing from fastrange(table_hash(key), cap) — capacities need
 //     not be powers of two, so a shard can fill whatever HBM it is given.
@@ -66,7 +67,19 @@ struct DevTable {
   // table) and slots per region (cap = rlen << rbits)
   uint32_t rbits;
   uint64_t rlen;
+  // 1: scalar kOptFTRLzn rows [z | n] — the value a pull returns is derived,
+  // ftrl_weight(z, n) with the four numbers below (pull_val); snapshots,
+  // commits, export and assign move the raw (z, n) bits
+  uint32_t zn;
+  float l1, l2, alpha, beta;
 };
+
+// What a pull of a scalar two-float row (a, b) hands out: a (the stored w) or,
+// for a [z | n] row, the derived weight.  t.zn is a kernel argument: the
+// branch is wave-uniform.
+__device__ __forceinline__ float pull_val(const DevTable& t, float a, float b) {
+  return t.zn ? ftrl_weight(a, b, t.l1, t.l2, t.alpha, t.beta) : a;
+}
 
 // The probe sequence of a key: home slot fastrange(table_hash, cap), then
 // linear inside [lo, hi) — the key's region (the whole table when rbits is

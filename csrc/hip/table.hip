@@ -117,6 +117,8 @@ __global__ __launch_bounds__(256) void k_gather(DevTable t, const long long* __r
     float* o = out + pos * (long long)t.dim;
     if (slot < 0) {
       for (uint32_t j = lg; j < t.dim; j += G) o[j] = 0.f;
+    } else if (t.zn) {  // [z | n] rows (dim 1): the derived weight
+      if (lg == 0) o[0] = pull_val(t, row_ld(t, slot, 0), row_ld(t, slot, 1));
     } else {
       for (uint32_t j = lg; j < t.dim; j += G) o[j] = row_ld(t, slot, j);
     }
@@ -202,7 +204,7 @@ __device__ __forceinline__ void pull_one(const DevTable& t, uint64_t key, long l
       wh.x = fresh_or(wh.x, ip, key, 0, 1);
       if (__float_as_uint(wh.y) == 0xFFFFFFFFu) wh.y = ip.state_init;
     }
-    o[0] = wh.x;
+    o[0] = pull_val(t, wh.x, wh.y);  // the snapshot keeps the row's own bits
     if (snap) snap[pos] = wh;
     ins += b;
     return;
@@ -223,9 +225,10 @@ __device__ __forceinline__ void pull_one(const DevTable& t, uint64_t key, long l
   float* o = out + pos * (long long)t.dim;
   if (slot < 0) {
     for (uint32_t j = lg; j < t.dim; j += G) o[j] = 0.f;
-  } else if (G == 1 && snap) {
+  } else if (G == 1 && (snap || t.zn)) {
     // scalar (w, h) rows, snapshot mode (see k_apply): one 8-byte row read,
-    // w to the model, (w, h) to the snapshot the apply updates from
+    // w to the model, (w, h) to the snapshot the apply updates from.  [z | n]
+    // rows come here with or without a snapshot: the pulled weight needs both
     float2 wh;
     if (inserted) {
       wh = make_float2(init_value(ip, key, 0, 1), ip.state_init);
@@ -235,8 +238,8 @@ __device__ __forceinline__ void pull_one(const DevTable& t, uint64_t key, long l
       wh.x = fresh_or(wh.x, ip, key, 0, 1);
       if (__float_as_uint(wh.y) == 0xFFFFFFFFu) wh.y = ip.state_init;
     }
-    o[0] = wh.x;
-    snap[pos] = wh;
+    o[0] = pull_val(t, wh.x, wh.y);
+    if (snap) snap[pos] = wh;
   } else {
     if (inserted) {
       for (uint32_t j = lg; j < t.width; j += G) {
@@ -429,8 +432,11 @@ __global__ __launch_bounds__(CT) void k_pull_claim_bk(
         wh.x = fresh_or(wh.x, ip, key[r], 0, 1);
         if (__float_as_uint(wh.y) == 0xFFFFFFFFu) wh.y = ip.state_init;
       }
-      if (out) out[pos] = wh.x;
-      if (occ && l < (uint32_t)kClaimMaxU) sv[l] = wh.x;
+      // what the model reads: w as stored or, for [z | n] rows, derived (a
+      // wave-uniform branch); the snapshot keeps the row's own bits
+      const float pv = pull_val(t, wh.x, wh.y);
+      if (out) out[pos] = pv;
+      if (occ && l < (uint32_t)kClaimMaxU) sv[l] = pv;
       snap[pos] = wh;
       ins += inserted;
     }
@@ -693,6 +699,10 @@ __global__ __launch_bounds__(256) void k_lookup_bk(DevTable t, const uint64_t* _
     }
     if (G > 1) slot = __shfl(slot, 0, G);
     float* o = out + ((long long)base + l) * (long long)t.dim;
+    if (t.zn) {  // [z | n] rows (dim 1): the derived weight
+      if (lg == 0) o[0] = slot < 0 ? 0.f : pull_val(t, row_ld(t, slot, 0), row_ld(t, slot, 1));
+      continue;
+    }
     for (uint32_t j = lg; j < t.dim; j += G) o[j] = slot < 0 ? 0.f : row_ld(t, slot, j);
   }
 }
@@ -708,13 +718,14 @@ __device__ __forceinline__ void apply_row(const DevTable& t, long long slot,
                                           const float* __restrict__ gr, const OptParams& op,
                                           int lg, const float2* __restrict__ snap = nullptr) {
   if (slot < 0) return;
-  if (G == 1 && t.dim == 1 && op.kind == kOptAdaGrad && !t.bf16 &&
+  if (G == 1 && t.dim == 1 && (op.kind == kOptAdaGrad || op.kind == kOptFTRLzn) && !t.bf16 &&
       t.row_off % 8 == 0 && t.stride % 8 == 0) {
     float* row = slot_row(t, slot);
-    // scalar-row AdaGrad (sparse LR): the (w, h) pair as one 8-byte load and
-    // one 8-byte store instead of two of each.  With a snapshot (the (w, h)
-    // the pull read, valid when nothing else wrote the row in between) the
-    // random read goes away: a coalesced read and a blind random store.
+    // scalar two-float rows (sparse LR: AdaGrad's (w, h), FTRL's (z, n)):
+    // the pair as one 8-byte load and one 8-byte store instead of two of
+    // each.  With a snapshot (the pair the pull read, valid when nothing else
+    // wrote the row in between) the random read goes away: a coalesced read
+    // and a blind random store.
     float2 wh = snap ? *snap : *reinterpret_cast<const float2*>(row);
     float s2 = 0.f;
     opt_update(op, wh.x, wh.y, s2, gr[0]);

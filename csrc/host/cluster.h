@@ -88,6 +88,12 @@ inline OptParams opt_from_config(const ConfigParser& c) {
     throw Error("optimizer: adam is not implemented by the native C++ cluster server (it keeps no "
                 "round count for the bias corrections); the Python servers implement it "
                 "(swiftsnails_amd HbmTable / HostTable behind PSEngine)");
+  // [z | n] rows need a pull that derives w: the HBM table's kernels do, the
+  // host table returns a row's leading floats as stored
+  if (k == "ftrl_zn")
+    throw Error("optimizer: ftrl_zn (FTRL in compact [z | n] rows) is not implemented by the "
+                "native C++ cluster server or the CPU host table; use ftrl here, or the GPU "
+                "servers (swiftsnails_amd HbmTable behind PSEngine)");
   OptParams op{};
   op.kind = k == "adagrad" ? kOptAdaGrad : k == "ftrl" ? kOptFTRL : kOptSGD;
   op.lr = std::stof(c.get("learning_rate", "0.01"));

@@ -206,6 +206,7 @@ class HostTable : NonCopyable {
             size_t cap_per_shard = 1024)
       : dim_(dim), width_(dim + opt_state_width(op.kind, dim)), ip_(ip), op_(op) {
     SS_CHECK(dim > 0 && shard_num > 0);
+    SS_CHECK_MSG(op.kind != kOptFTRLzn, "ftrl_zn ([z | n] rows) is not implemented by the host table");
     for (int i = 0; i < shard_num; ++i)
       shards_.emplace_back(new HostShard(dim_, width_, cap_per_shard));
     if (nthreads <= 0) nthreads = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
@@ -218,6 +219,7 @@ class HostTable : NonCopyable {
   int to_shard_id(uint64_t key) const { return (int)(fmix64(key) % (uint64_t)shards_.size()); }
   void set_opt(const OptParams& op) {
     SS_CHECK_MSG(dim_ + opt_state_width(op.kind, dim_) == width_, "optimizer state width differs");
+    SS_CHECK_MSG(op.kind != kOptFTRLzn, "ftrl_zn ([z | n] rows) is not implemented by the host table");
     op_ = op;
   }
   const OptParams& opt() const { return op_; }

@@ -5,9 +5,13 @@
 //
 // A row is a victim iff every condition that is set holds:
 //   w_below    max_j |w_j| <= w_below over the `dim` parameters (zero-init LR
-//              and FTRL with L1: dead weights are exactly 0)
+//              and FTRL with L1: dead weights are exactly 0).  A kOptFTRLzn
+//              row stores no w: the condition is on the derived weight
+//              ftrl_weight(z, n), which the caller's `ld(j)` returns for
+//              j < dim (evict.hip k_evict_mark)
 //   acc_below  max_j acc_j <= acc_below over the optimizer's sum-of-squares
-//              block (AdaGrad s1, FTRL n = s2, Adam v = s2; SGD has none).
+//              block (AdaGrad s1, FTRL n = s2, FTRLzn n = s1, Adam v = s2; SGD
+//              has none).
 //              With a key-seeded initialiser this loses nothing: a key whose
 //              accumulator is tiny has barely moved from the initial row it
 //              gets back when it returns.
@@ -30,8 +34,9 @@ struct EvictRule {
 // index of the first float of the sum-of-squares block inside a row
 // (parameters, then optimizer state), -1 for a rule without one
 SS_HD int evict_acc_offset(int opt_kind, int dim) {
-  return opt_kind == kOptAdaGrad ? dim
-                                 : ((opt_kind == kOptFTRL || opt_kind == kOptAdam) ? 2 * dim : -1);
+  return (opt_kind == kOptAdaGrad || opt_kind == kOptFTRLzn)
+             ? dim
+             : ((opt_kind == kOptFTRL || opt_kind == kOptAdam) ? 2 * dim : -1);
 }
 
 // `ld(j)`: coordinate j of the row as fp32.  acc_off: evict_acc_offset.

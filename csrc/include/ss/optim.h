@@ -23,7 +23,10 @@ namespace ss {
 enum InitKind : int { kInitZero = 0, kInitUniform = 1, kInitNormal = 2, kInitConst = 3,
                       kInitMarker = 4 };
 static constexpr uint32_t kInitMarkerBits = 0x7FBADBADu;
-enum OptKind : int { kOptSGD = 0, kOptAdaGrad = 1, kOptFTRL = 2, kOptAdam = 3 };
+// kOptFTRLzn: FTRL-Proximal in compact [z | n] rows (dim 1): no w is stored,
+// a pull derives it (ftrl_weight), so a scalar row is the 16-byte [z | n | key]
+// slot the region tables, the pull snapshot and the fused merge work on.
+enum OptKind : int { kOptSGD = 0, kOptAdaGrad = 1, kOptFTRL = 2, kOptAdam = 3, kOptFTRLzn = 4 };
 
 struct InitParams {
   int kind;
@@ -47,7 +50,9 @@ struct OptParams {
 };
 
 SS_HD int opt_state_width(int kind, int dim) {
-  return kind == kOptAdaGrad ? dim : ((kind == kOptFTRL || kind == kOptAdam) ? 2 * dim : 0);
+  return (kind == kOptAdaGrad || kind == kOptFTRLzn)
+             ? dim
+             : ((kind == kOptFTRL || kind == kOptAdam) ? 2 * dim : 0);
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -85,10 +90,19 @@ SS_HD float init_value(const InitParams& ip, uint64_t key, uint32_t j, uint32_t 
   return std::sqrt(-2.0f * SS_LOGF(u1)) * SS_COSF(6.2831853f * u2) * ip.scale;
 }
 
+// The FTRL-Proximal weight of a coordinate's (z, n): what kOptFTRL stores as
+// w after a step and what a pull of a kOptFTRLzn row returns.  The zero is +0.
+SS_HD float ftrl_weight(float z, float n, float l1, float l2, float alpha, float beta) {
+  return std::fabs(z) <= l1
+             ? 0.0f
+             : -(z - std::copysign(l1, z)) / ((beta + std::sqrt(n)) / alpha + l2);
+}
+
 // One coordinate of an optimizer step. `row` = params, `st` = state base.
 // Register form: w = parameter, s1/s2 = the optimizer state slots of this
 // coordinate (AdaGrad: s1 = sum g^2; FTRL: s1 = z, s2 = n; Adam: s1 = m,
-// s2 = v).  Kernels load a row's coordinates first, update in registers and
+// s2 = v; FTRLzn: w = z, s1 = n — the row's two floats in storage order).
+// Kernels load a row's coordinates first, update in registers and
 // store after (no load behind a store of the same row).
 SS_HD void opt_update(const OptParams& op, float& w, float& s1, float& s2, float g) {
   g *= op.grad_scale;
@@ -109,10 +123,16 @@ SS_HD void opt_update(const OptParams& op, float& w, float& s1, float& s2, float
       const float sigma = (std::sqrt(n2) - std::sqrt(s2)) / op.ftrl_alpha;
       s1 += g - sigma * w;
       s2 = n2;
-      const float az = std::fabs(s1);
-      w = az <= op.l1 ? 0.0f
-                      : -(s1 - std::copysign(op.l1, s1)) /
-                            ((op.ftrl_beta + std::sqrt(n2)) / op.ftrl_alpha + op.l2);
+      w = ftrl_weight(s1, n2, op.l1, op.l2, op.ftrl_alpha, op.ftrl_beta);
+    } break;
+    case kOptFTRLzn: {
+      // the same step on a [z | n] row (w = z, s1 = n): the weight the step
+      // needs is derived from the row, none is stored
+      const float wv = ftrl_weight(w, s1, op.l1, op.l2, op.ftrl_alpha, op.ftrl_beta);
+      const float n2 = s1 + g * g;
+      const float sigma = (std::sqrt(n2) - std::sqrt(s1)) / op.ftrl_alpha;
+      w += g - sigma * wv;
+      s1 = n2;
     } break;
     case kOptAdam: {
       g += op.l2 * w;
@@ -125,7 +145,7 @@ SS_HD void opt_update(const OptParams& op, float& w, float& s1, float& s2, float
 
 // number of state floats per coordinate
 SS_HD int opt_state_per_coord(int kind) {
-  return kind == kOptSGD ? 0 : (kind == kOptAdaGrad ? 1 : 2);
+  return kind == kOptSGD ? 0 : ((kind == kOptAdaGrad || kind == kOptFTRLzn) ? 1 : 2);
 }
 
 SS_HD void opt_apply(const OptParams& op, float* row, float* st, uint32_t dim, uint32_t j,

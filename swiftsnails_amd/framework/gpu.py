@@ -314,7 +314,9 @@ def build_worker(cfg: Config):
     nserv = len(_ranks(cfg.get("server_ranks"), world))
     load = float(cfg.get("table_load", 0.7))
     opt = Optimizer(cfg.get("optimizer", "adagrad"), lr=float(cfg.get("learning_rate", 0.05)),
-                    l1=float(cfg.get("l1", 0.0)), l2=float(cfg.get("l2", 0.0)))
+                    l1=float(cfg.get("l1", 0.0)), l2=float(cfg.get("l2", 0.0)),
+                    ftrl_alpha=float(cfg.get("ftrl_alpha", 0.05)),
+                    ftrl_beta=float(cfg.get("ftrl_beta", 1.0)))
     rank = int(os.environ.get("RANK", "0"))
     dev = None
     if torch.cuda.is_available():  # the rank's device before data is uploaded to it

@@ -173,7 +173,7 @@ class SparseLRWorker(PipelinedWorker):
             # N>1 record exchange: the rows came back per occurrence at its
             # send-segment position (the forward reads occ[pos_of[j]] there),
             # the gradients go out the same way — no worker merge; the
-            # servers merge per distinct key with the AdaGrad update fused
+            # servers merge per distinct key with the scalar-row update fused
             o, eng = dd.owner, self.engine
             own = rnd.own_vals is not None and self.gring is not None
             # ... and their gradients handed to the server merge in place,
@@ -202,7 +202,8 @@ class SparseLRWorker(PipelinedWorker):
             h.lr_fwd_g(0, xp, self.labels[slot].data_ptr(), d.batch_size, d.num_fields,
                        rnd.uvals.data_ptr(), self.gocc.data_ptr(), 1, self._acc.data_ptr(),
                        0, st, o.index_ptrs(dd.n), occ=self.occ.data_ptr())
-            # one GPU: the merge kernel runs the AdaGrad update itself
+            # one GPU: the merge kernel runs the update itself (scalar
+            # two-float rows: AdaGrad, ftrl_zn)
             # (engine.fuse_apply: pull snapshot still valid), push() then only
             # does the bookkeeping; N>1: compact rows in the send layout
             fa = self.engine.fuse_apply(rnd)

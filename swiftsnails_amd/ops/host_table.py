@@ -63,6 +63,10 @@ class HostTable:
                  init: Optional[InitConfig] = None, nthreads: int = 0):
         self.dim = int(dim)
         self.opt = optimizer or Optimizer()
+        if self.opt.kind == "ftrl_zn":
+            # [z | n] rows need a pull that derives w (the HBM table's kernels)
+            raise ValueError("optimizer ftrl_zn (FTRL in compact [z | n] rows) is not implemented "
+                             "by the CPU HostTable; use ftrl here, or HbmTable on a GPU")
         self.init_cfg = init or InitConfig()
         self._t = host().HostTable(self.dim, shard_num, _host_init(self.init_cfg),
                                    _host_opt(self.opt), nthreads)

@@ -9,7 +9,9 @@ these are compiled device functors (``ss_device.h``: ``init_value`` and
 probe/apply kernels:
 
 * init  : zero | uniform ``(u-0.5)*scale`` (word2vec convention, vec1.h:223-226) | normal
-* push  : SGD | AdaGrad | FTRL-Proximal | lazy Adam (+ L1/L2, gradient scale, clip)
+* push  : SGD | AdaGrad | FTRL-Proximal | lazy Adam (+ L1/L2, gradient scale, clip);
+  ``ftrl_zn``: FTRL-Proximal in compact ``[z | n]`` rows (scalar tables): no
+  ``w`` is stored, a pull derives it (``pull_reference``)
 * merge : summation of duplicate-key gradients (done worker-side before push)
 
 ``apply_reference`` is the float32 numpy implementation of the same update,
@@ -23,7 +25,7 @@ from typing import Optional
 
 import numpy as np
 
-OPT_KINDS = {"sgd": 0, "adagrad": 1, "ftrl": 2, "adam": 3}
+OPT_KINDS = {"sgd": 0, "adagrad": 1, "ftrl": 2, "adam": 3, "ftrl_zn": 4}
 # compiled initialisers (ss/optim.h init_value); "marker" is internal: the
 # placeholder a tensor-code initialiser replaces (HbmTable.set_init_method)
 INIT_KINDS = {"zero": 0, "uniform": 1, "normal": 2, "const": 3, "marker": 4}
@@ -31,7 +33,9 @@ INIT_MARKER_BITS = 0x7FBADBAD
 
 
 def state_width(kind: str, dim: int) -> int:
-    return {"sgd": 0, "adagrad": dim, "ftrl": 2 * dim, "adam": 2 * dim}[kind]
+    """Optimizer-state floats beside a row's ``dim`` leading floats (for
+    ``ftrl_zn`` the leading float is ``z`` and the state ``n``)."""
+    return {"sgd": 0, "adagrad": dim, "ftrl": 2 * dim, "adam": 2 * dim, "ftrl_zn": dim}[kind]
 
 
 @dataclass
@@ -67,6 +71,12 @@ class Optimizer:
     def __post_init__(self):
         if self.kind not in OPT_KINDS:
             raise ValueError(f"unknown optimizer {self.kind!r}; have {sorted(OPT_KINDS)}")
+        if self.kind == "ftrl_zn":
+            # the pulled weight divides by (beta + sqrt(n)) / alpha + l2
+            if not self.ftrl_alpha > 0:
+                raise ValueError("ftrl_zn: ftrl_alpha must be > 0")
+            if self.l1 < 0 or self.l2 < 0 or self.ftrl_beta < 0:
+                raise ValueError("ftrl_zn: l1, l2 and ftrl_beta must be >= 0")
 
     def state_width(self, dim: int) -> int:
         return state_width(self.kind, dim)
@@ -97,7 +107,8 @@ class Optimizer:
         """Build from a ConfigParser-like mapping (keys: optimizer, learning_rate, ...)."""
         g = (lambda k, d: cfg.get(prefix + k, d)) if hasattr(cfg, "get") else (lambda k, d: d)
         return cls(kind=str(g("optimizer", "adagrad")), lr=float(g("learning_rate", 0.05)),
-                   l1=float(g("l1", 0.0)), l2=float(g("l2", 0.0)))
+                   l1=float(g("l1", 0.0)), l2=float(g("l2", 0.0)),
+                   ftrl_alpha=float(g("ftrl_alpha", 0.05)), ftrl_beta=float(g("ftrl_beta", 1.0)))
 
 
 @dataclass
@@ -108,7 +119,8 @@ class EvictRule:
     parameters; ``acc_below``: ``max_j acc_j <= acc_below`` over the
     optimizer's sum-of-squares block (AdaGrad's accumulator, FTRL's ``n``,
     Adam's ``v``; SGD has none).  Comparisons are on fp32 values; a NaN
-    coordinate keeps the row."""
+    coordinate keeps the row.  An ``ftrl_zn`` row stores no ``w``:
+    ``w_below`` is evaluated on the derived weight (``pull_reference``)."""
     w_below: Optional[float] = None
     acc_below: Optional[float] = None
 
@@ -182,6 +194,14 @@ def apply_reference(opt: Optimizer, rows: np.ndarray, grads: np.ndarray, dim: in
         neww = -(z - np.sign(z) * f32(opt.l1)) / ((f32(opt.ftrl_beta) + np.sqrt(n2)) /
                                                    f32(opt.ftrl_alpha) + f32(opt.l2))
         rows[:, :dim] = np.where(np.abs(z) <= opt.l1, f32(0), neww)
+    elif opt.kind == "ftrl_zn":
+        # [z | n] rows: the step's w is derived from the row, none is stored
+        z, n = rows[:, :dim], rows[:, dim:2 * dim]
+        wv = pull_reference(opt, rows, dim)
+        n2 = n + g * g
+        sigma = (np.sqrt(n2) - np.sqrt(n)) / f32(opt.ftrl_alpha)
+        rows[:, :dim] = z + (g - sigma * wv)
+        rows[:, dim:2 * dim] = n2
     elif opt.kind == "adam":
         bc1, bc2 = opt.bias_corrections()
         g = g + f32(opt.l2) * w
@@ -193,5 +213,22 @@ def apply_reference(opt: Optimizer, rows: np.ndarray, grads: np.ndarray, dim: in
     return rows
 
 
-__all__ = ["Optimizer", "InitConfig", "apply_reference", "init_reference", "state_width",
+def pull_reference(opt: Optimizer, rows: np.ndarray, dim: int) -> np.ndarray:
+    """fp32 reference of what a pull returns for full rows [n, width]: the
+    stored parameters, or for ``ftrl_zn`` rows the derived weight
+    (ss::ftrl_weight): +0 where ``|z| <= l1``, else
+    ``-(z - sign(z) l1) / ((beta + sqrt(n)) / alpha + l2)``."""
+    rows = np.asarray(rows, np.float32)
+    if opt.kind != "ftrl_zn":
+        return rows[:, :dim].copy()
+    f32 = np.float32
+    z, n = rows[:, :dim], rows[:, dim:2 * dim]
+    with np.errstate(invalid="ignore"):
+        w = -(z - np.copysign(f32(opt.l1), z)) / ((f32(opt.ftrl_beta) + np.sqrt(n)) /
+                                                  f32(opt.ftrl_alpha) + f32(opt.l2))
+    return np.where(np.abs(z) <= f32(opt.l1), f32(0), w).astype(np.float32)
+
+
+__all__ = ["Optimizer", "InitConfig", "apply_reference", "pull_reference", "init_reference",
+           "state_width",
            "OPT_KINDS", "INIT_KINDS", "math"]

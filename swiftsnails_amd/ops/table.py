@@ -128,6 +128,8 @@ class HbmTable:
         self.G = lane_group or int(os.environ.get("SS_TABLE_G", "0")) or \
             default_lane_group(self.width)
         self.max_load = max_load
+        if self.opt.kind == "ftrl_zn":
+            self._check_zn()
         # bumped by every row-modifying call: a pull snapshot (pull_buckets
         # snap=) is valid for a blind-write apply only while it is unchanged
         self.version = 0
@@ -139,6 +141,32 @@ class HbmTable:
         self.pull_fn = None
         self._alloc(int(capacity))
         self._init_native = self.init_cfg.native()
+
+    @property
+    def zn(self) -> bool:
+        """Rows are FTRL ``[z | n]`` pairs: a pull returns the derived weight.
+        The pull kernels take ``l1``, ``l2``, ``ftrl_alpha`` and ``ftrl_beta``
+        from the table descriptor, which ``set_optimizer`` rebuilds: it is
+        the only supported way to change them.  Assigning to ``table.opt.l1``
+        in place leaves the pulls on the old values while the update uses the
+        new ones."""
+        return self.opt.kind == "ftrl_zn"
+
+    def _check_zn(self) -> None:
+        """``ftrl_zn`` rows: a new key is (z, n) = (0, 0), i.e. w = 0, which
+        is what an EMPTY slot of a zero-initialised table already holds."""
+        if self.init_cfg.kind != "zero":
+            raise ValueError(f"ftrl_zn needs InitConfig('zero'), not {self.init_cfg.kind!r}: a "
+                             "new key is (z, n) = (0, 0)")
+        if float(self.init_cfg.state_init) != 0.0:
+            raise ValueError(f"ftrl_zn needs state_init == 0, not {self.init_cfg.state_init}: a "
+                             "new key's n is 0")
+        if self.dim != 1:
+            raise ValueError(f"ftrl_zn needs dim == 1 (scalar rows), not {self.dim}")
+        if self.row_dtype != "fp32":
+            raise ValueError(f"ftrl_zn needs row_dtype 'fp32', not {self.row_dtype!r}")
+        if self.G != 1:
+            raise ValueError(f"ftrl_zn needs lane group 1, not {self.G}")
 
     # -- storage ------------------------------------------------------------
     def _region_bits(self, cap: int) -> int:
@@ -187,7 +215,10 @@ class HbmTable:
         self.dt = hip().DevTable(self.storage.data_ptr(), self.capacity, self.stride,
                                  self.key_off, self.dim, self.width,
                                  int(self.prefilled and self.init_fn is None), self.row_off,
-                                 int(self.bf16), self.rbits)
+                                 int(self.bf16), self.rbits,
+                                 # [z | n] rows: what the pull kernels derive w with
+                                 int(self.zn), float(self.opt.l1), float(self.opt.l2),
+                                 float(self.opt.ftrl_alpha), float(self.opt.ftrl_beta))
 
     @staticmethod
     def plan(n_keys: int, dim: int, optimizer: Optional[Optimizer] = None,
@@ -207,9 +238,21 @@ class HbmTable:
         return self.capacity * self.stride
 
     def set_optimizer(self, opt: Optimizer):
+        """Replace the update rule's hyperparameters (same row layout and
+        meaning).  Rebuilds the table descriptor and bumps ``version``: for
+        ``ftrl_zn`` the pulled weight depends on them, so change them here
+        and never by mutating ``table.opt`` in place."""
         if opt.state_width(self.dim) != self.width - self.dim:
             raise ValueError("optimizer state width differs from the table layout")
+        if (opt.kind == "ftrl_zn") != self.zn:
+            # AdaGrad's (w, h) and FTRL's (z, n) have one width, not one meaning
+            raise ValueError(f"cannot change a table of {self.opt.kind} rows to {opt.kind}: "
+                             "ftrl_zn rows hold (z, n), not a stored w")
         self.opt = opt
+        # the pull kernels derive an ftrl_zn weight from the hyperparameters
+        # in the table descriptor; a snapshot's pulled values are stale
+        self._make_dt()
+        self.version += 1
 
     # -- hot path -----------------------------------------------------------
     def _seg(self, n: int):
@@ -254,11 +297,13 @@ class HbmTable:
 
     @property
     def snapshot_ok(self) -> bool:
-        """Rows are (w, h) scalar AdaGrad pairs the pull can snapshot."""
+        """Rows are scalar two-float pairs the pull can snapshot: AdaGrad's
+        (w, h) or FTRL's (z, n)."""
         return (self.G == 1 and self.dim == 1 and self.width == 2 and self.push_fn is None and
                 not self.bf16 and
                 not self.custom_pull and
-                self.opt.kind == "adagrad" and self.stride % 8 == 0 and self.row_off % 8 == 0)
+                self.opt.kind in ("adagrad", "ftrl_zn") and self.stride % 8 == 0 and
+                self.row_off % 8 == 0)
 
     # -- user-defined access methods (tensor code) ---------------------------
     @property
@@ -273,6 +318,8 @@ class HbmTable:
         state) of keys a pull creates.  The device insert writes a NaN marker
         row; ``finish_pull`` finds the marked rows among a pull's and replaces
         them.  ``None`` restores the compiled initialiser."""
+        if fn is not None and self.zn:
+            raise ValueError("ftrl_zn rows start at (z, n) = (0, 0): no initialiser method")
         was = self.init_fn
         self.init_fn = fn
         self._init_native = (InitConfig("marker", state_init=self.init_cfg.state_init).native()
@@ -400,7 +447,7 @@ class HbmTable:
         ``push_slots(snap=)`` that needs no random row read."""
         bkeys, bstart, unum, ubase, P = view
         if snap is not None and not self.snapshot_ok:
-            raise ValueError("pull snapshot needs scalar AdaGrad rows (dim 1, G 1)")
+            raise ValueError("pull snapshot needs scalar AdaGrad or ftrl_zn rows (dim 1, G 1)")
         hip().pull_unique_bk(self.dt, bkeys, bstart, unum, ubase, P, slots.data_ptr(),
                              out.data_ptr(), self._init_native, self.size_ctr.data_ptr(),
                              self.err.data_ptr(), self.G, _stream_ptr(stream),
@@ -645,13 +692,25 @@ class HbmTable:
         return self.evict(mask=mask, stream=stream)
 
     # -- dense views (tests / small tables) --------------------------------
+    def weights(self, rows) -> np.ndarray:
+        """The parameters [m, dim] of exported rows [m, width] (``export`` /
+        a checkpoint's rows): the leading ``dim`` floats, or for ``ftrl_zn``
+        rows the weight derived from (z, n) — what a pull returns."""
+        from .optim import pull_reference
+
+        r = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+        return pull_reference(self.opt, r.reshape(-1, self.width), self.dim)
+
     def to_dict(self, with_state: bool = False) -> dict[int, np.ndarray]:
+        """key -> parameters (``with_state``: the raw row; an ``ftrl_zn`` row is
+        (z, n), its parameter the derived weight)."""
         out = {}
         for k, r in self.export():
             kn = k.numpy().view(np.uint64)
             rn = r.numpy()
+            wn = None if with_state else self.weights(rn)
             for i in range(len(kn)):
-                out[int(kn[i])] = rn[i] if with_state else rn[i, :self.dim]
+                out[int(kn[i])] = rn[i] if with_state else wn[i]
         return out
 
     def __len__(self):

@@ -253,7 +253,8 @@ class PSEngine(HostRounds, DeviceSetup, EngineControl):
         self.claim_rounds = False
         self.claim_occ: Optional[torch.Tensor] = None
         if self.fast1:
-            # pull snapshots for the blind-write apply (scalar AdaGrad rows)
+            # pull snapshots for the blind-write apply (scalar two-float rows:
+            # AdaGrad's (w, h), ftrl_zn's (z, n))
             self.snapshot = bool(getattr(table, "snapshot_ok", False))
             # ... whose slot indices the pull stores as 4 bytes when the shard
             # has fewer than 2^31 slots (the fused merge reads them back):
@@ -277,7 +278,7 @@ class PSEngine(HostRounds, DeviceSetup, EngineControl):
             # claimed pulls (region tables, table.hip k_pull_claim_bk): the
             # dedup buckets whole table regions, the bucket's pull claims new
             # keys' slots in LDS (no device-scope CAS, nothing written), and
-            # the fused merge stores [w | h | key] per slot (SS_CLAIM=0: off)
+            # the fused merge stores [row | key] per slot (SS_CLAIM=0: off)
             self.claim = bool(self.slot32 and getattr(table, "rbits", 0) and
                               os.environ.get("SS_CLAIM", "1") != "0")
             if self.claim:
@@ -583,15 +584,16 @@ class PSEngine(HostRounds, DeviceSetup, EngineControl):
     # ------------------------------------------------------------ stage 3
     def _server_update_kind(self) -> Optional[str]:
         """How the server merge applies the update: fused into the merge for
-        scalar AdaGrad rows ("scalar") and for wider rows ("rows": lane c of
-        a key's lane group updates coordinate c); None: merged rows first,
-        then the apply kernel (other scalar rules) or a tensor-code rule."""
+        scalar two-float rows ("scalar": AdaGrad's (w, h), ftrl_zn's (z, n))
+        and for wider rows ("rows": lane c of a key's lane group updates
+        coordinate c); None: merged rows first, then the apply kernel (other
+        scalar rules) or a tensor-code rule."""
         tab = self.table
         if tab is None or tab.push_fn is not None:
             return None
         if self.dim > 1:
             return "rows"
-        if (tab.opt.kind == "adagrad" and tab.width == 2 and tab.G == 1 and
+        if (tab.opt.kind in ("adagrad", "ftrl_zn") and tab.width == 2 and tab.G == 1 and
                 not getattr(tab, "bf16", False)):
             return "scalar"
         return None
@@ -600,8 +602,8 @@ class PSEngine(HostRounds, DeviceSetup, EngineControl):
         """Record exchange: whether a round may take the own-record shortcut —
         this rank's own records' rows in the cached ``own_vals`` buffer and
         their gradients read by the server merge straight from the worker's
-        per-sample gradient (``Round.own_grad``).  Only the fused scalar
-        AdaGrad merge reads gradients that way, and not through the staging
+        per-sample gradient (``Round.own_grad``).  Only the fused merge of
+        scalar two-float rows reads gradients that way, and not through the staging
         buffer: every other rule (SGD, bf16 rows, a tensor-code push method,
         SS_SRV_STAGE=1) sends its own records through the arena like the
         peers'.  Asked per round — by the pull, by the worker's compute and by
@@ -627,8 +629,8 @@ class PSEngine(HostRounds, DeviceSetup, EngineControl):
     def fuse_apply(self, rnd: Round, snapshot: bool = True) -> Optional[dict]:
         """Arguments that let a model's gradient-merge kernel run the optimizer
         update itself (``bd_reduce(..., **args)`` / ``bd_reduce_fm``), or
-        None.  One GPU; ``snapshot``: scalar AdaGrad rows from the pull's
-        still-valid (w, h) snapshot (blind store).  Marks the round applied."""
+        None.  One GPU; ``snapshot``: scalar two-float rows (AdaGrad's (w, h),
+        ftrl_zn's (z, n)) from the pull's still-valid snapshot (blind store).  Marks the round applied."""
         tab = self.table
         if not (self.fast1 and not rnd.applied and rnd.slots is not None
                 and getattr(tab, "push_fn", None) is None):
@@ -643,7 +645,7 @@ class PSEngine(HostRounds, DeviceSetup, EngineControl):
                 "slot32": int(rnd.slot32)}
         if snapshot:
             args["snap"] = rnd.snap.data_ptr()
-        if rnd.deferred:  # the merge stores whole [w | h | key] slots
+        if rnd.deferred:  # the merge stores whole [row | key] slots
             args["bkeys"] = rnd.dd.owner.bkeys.data_ptr()
             self._claimed = [x for x in self._claimed if x is not rnd]
             rnd.deferred = False

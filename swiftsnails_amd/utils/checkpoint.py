@@ -17,6 +17,17 @@ Here (works for ``HbmTable`` and ``HostTable``):
   rows[n, width]``, the fast default for large tables.  Both stream: host
   memory is one export / load chunk regardless of the shard size (a 288 GB
   HBM shard does not have to fit in host RAM).
+* ``ftrl_zn`` tables (rows ``[z | n]``, no stored ``w``): the binary and the
+  with-state text formats hold the raw (z, n) and resume bit for bit; text
+  without state is ``key<TAB>w`` with the derived weight — the model, as the
+  reference's dump is — and cannot be loaded back into such a table.  The
+  binary header records the row rule (``"row_rule": "zn"``), and a load
+  refuses a file whose rule differs from the table's: an AdaGrad (w, h) file
+  has the same width and would otherwise load as (z, n).  The text format
+  carries no rule tag: a ``with_state`` text dump of an AdaGrad table has the
+  layout of an ``ftrl_zn`` one and loads into it as (z, n) — the caller keeps
+  text dumps of the two rules apart (``load_text`` refuses only dumps without
+  state).
 * sharded checkpoints: one file per server rank
   (``<prefix>.shard<r>-of-<N>.<ext>``); ``load_sharded`` re-routes every key
   through the current router, so a job can resume on a different world size.
@@ -44,6 +55,20 @@ def _iter_export(table) -> Iterable[tuple[np.ndarray, np.ndarray]]:
                r.numpy() if isinstance(r, torch.Tensor) else r)
 
 
+def _zn(table) -> bool:
+    """``table`` holds ftrl_zn rows ``[z | n]`` (no stored w)."""
+    return getattr(getattr(table, "opt", None), "kind", None) == "ftrl_zn"
+
+
+def _text_rows(table, r: np.ndarray, with_state: bool):
+    """(rows, width) as ``format_rows`` prints them: the raw rows, or for an
+    ftrl_zn table dumped without state the derived weights alone."""
+    r = np.ascontiguousarray(r, dtype=np.float32)
+    if _zn(table) and not with_state:
+        return np.ascontiguousarray(table.weights(r), dtype=np.float32), table.dim
+    return r, table.width
+
+
 def save_text(table, path: str, precision: int = 9, with_state: bool = False) -> int:
     """Write ``key\\tv0 v1 ...`` lines; returns the number of keys written.
 
@@ -58,9 +83,9 @@ def save_text(table, path: str, precision: int = 9, with_state: bool = False) ->
         import sys
 
         for k, r in _iter_export(table):
+            rows, width = _text_rows(table, r, with_state)
             sys.stdout.buffer.write(h.format_rows(
-                np.ascontiguousarray(k), np.ascontiguousarray(r, dtype=np.float32),
-                table.dim, table.width, with_state, precision))
+                np.ascontiguousarray(k), rows, table.dim, width, with_state, precision))
             n += len(k)
         sys.stdout.buffer.flush()
         return n
@@ -68,9 +93,9 @@ def save_text(table, path: str, precision: int = 9, with_state: bool = False) ->
     try:
         with open(tmp, "wb") as out:
             for k, r in _iter_export(table):
-                out.write(h.format_rows(np.ascontiguousarray(k),
-                                        np.ascontiguousarray(r, dtype=np.float32),
-                                        table.dim, table.width, with_state, precision))
+                rows, width = _text_rows(table, r, with_state)
+                out.write(h.format_rows(np.ascontiguousarray(k), rows, table.dim, width,
+                                        with_state, precision))
                 n += len(k)
             out.flush()
             os.fsync(out.fileno())
@@ -116,7 +141,19 @@ def iter_text(path: str, dim: int, width: int, state_init: float = 0.0,
             yield h.parse_rows(tail, dim, width, state_init)
 
 
+def _text_has_state(path: str) -> bool:
+    """The dump's first line carries a `` | state`` tail."""
+    with open(path, "rb") as f:
+        for line in f:
+            if line.strip():
+                return b"|" in line
+    return True  # no rows: nothing to refuse
+
+
 def load_text(table, path: str, key_filter=None) -> int:
+    if _zn(table) and not _text_has_state(path):
+        raise ValueError(f"{path}: a text dump without state holds the weights alone; an ftrl_zn "
+                         "table resumes from (z, n) — load a with_state=True or binary checkpoint")
     n = 0
     for keys, rows in iter_text(path, table.dim, table.width, table.init_cfg.state_init):
         if key_filter is not None:
@@ -151,6 +188,8 @@ def save_binary(table, path: str, meta: Optional[dict] = None) -> int:
     w = table.width
     hdr = json.dumps({"dim": table.dim, "width": w, "n": n,
                       "optimizer": table.opt.kind, "opt_step": table.opt.step,
+                      # rows [z | n] (absent: rows that start with a stored w)
+                      **({"row_rule": "zn"} if _zn(table) else {}),
                       **(meta or {})}).encode()
     off = 12 + len(hdr)
     tmp = path + ".tmp"
@@ -208,6 +247,11 @@ def load_binary(table, path: str, key_filter=None, chunk: int = 1 << 22) -> int:
     if hdr["width"] != table.width or hdr["dim"] != table.dim:
         raise ValueError(f"checkpoint layout dim={hdr['dim']} width={hdr['width']} != table "
                          f"dim={table.dim} width={table.width}")
+    rule, want = hdr.get("row_rule", "w"), "zn" if _zn(table) else "w"
+    if rule != want:
+        names = {"w": "a stored w first (sgd / adagrad / ftrl / adam)", "zn": "ftrl_zn's (z, n)"}
+        raise ValueError(f"{path}: checkpoint rows hold {names.get(rule, rule)}, the table's "
+                         f"{names[want]}")
     n = 0
     for keys, rows in iter_binary(path, chunk):
         if key_filter is not None:
