@@ -103,14 +103,6 @@ int bd_target_dist() {
 // (every call and helper of a deduper passes the same ndest), not of the
 // process: engines of either kind can coexist.
 static constexpr int kBdRecLayout = 1 << 16;
-// ... with kBdRecGroup as well (N>1 grouped records, round 6): the record
-// placement but the unique layout's fuller source buckets (~3072
-// occurrences); a pass after the scatter (k_rec_group) groups each bucket's
-// records by the servers' sub-bucket, as the unique dedup groups its keys,
-// so a server reads exact ranges.  The small buckets above (3584 / N) made
-// the scatter's tile runs shorter than a sector at N >= 4 (P = 11K-16K
-// buckets, 8K- down to 2K-key tiles)
-static constexpr int kBdRecGroup = 1 << 17;
 static int bd_target(int nranks, bool rec) {
   static const int one = [] {
     const char* e = std::getenv("SS_BD_TARGET");
@@ -121,7 +113,6 @@ static int bd_target(int nranks, bool rec) {
   return nranks > 1 ? bd_target_dist() : one;
 }
 int bd_record_layout_bit() { return kBdRecLayout; }
-int bd_record_group_bit() { return kBdRecGroup; }
 // the occurrences-per-bucket target a layout of `nranks` ranks uses
 int bd_target_for(int nranks, bool records) { return bd_target(nranks, records); }
 static constexpr int kBdTS = 4096;      // LDS hash slots per bucket
@@ -151,16 +142,6 @@ __device__ __forceinline__ uint32_t bd_bucket(uint64_t key, const RouteSpec& rs,
   return d * Pd + __umulhi(h, Pd);
 }
 
-// SS_BD_XCD=1: the scatter's chunks in XCD-aware order (measured neutral:
-// bench 0.779-0.784 vs 0.784-0.786 ms, the same WRITE_SIZE)
-static int bd_xcd() {
-  static const int v = [] {
-    const char* e = std::getenv("SS_BD_XCD");
-    return e ? std::atoi(e) : 0;
-  }();
-  return v;
-}
-
 // upper bound on count/scatter chunks (SS_BD_NCH knob): 128 — a chunk of the
 // bench batch (10.2M keys) is 80K keys, looped in 8192-key register tiles, so
 // each (chunk, bucket) run of positions is ~16 long and the scatter's
@@ -188,13 +169,13 @@ struct BdLayout {
 };
 
 static int bd_clamp_ndest(int nranks, int ndest) {
-  ndest &= ~(kBdRecLayout | kBdRecGroup);
+  ndest &= ~kBdRecLayout;
   return ndest < 1 || ndest > nranks ? nranks : ndest;
 }
 
 static BdLayout bd_layout(long long n, int nranks, int ndest) {
   BdLayout L{};
-  const bool rec = (ndest & kBdRecLayout) != 0 && !(ndest & kBdRecGroup);
+  const bool rec = (ndest & kBdRecLayout) != 0;
   ndest = bd_clamp_ndest(nranks, ndest);
   // ~2048 occurrences per bucket, but at least ~1024 buckets for small calls
   // (>= 4 workgroups per CU; a word2vec step of 196K keys got only 96 buckets)
@@ -246,7 +227,7 @@ long long bd_max_keys() { return (long long)kBdMaxBuckets * 2800; }
 long long bd_scratch_words(long long n, int nranks, int ndest) {
   if (n < 1) n = 1;
   const int ndest_arg = ndest;
-  const bool rec = (ndest & kBdRecLayout) != 0 && !(ndest & kBdRecGroup);
+  const bool rec = (ndest & kBdRecLayout) != 0;
   ndest = bd_clamp_ndest(nranks, ndest);
   // active buckets (those of receiving destinations), then all P = Pd * nranks
   const int tg = bd_target(nranks, rec);
@@ -441,18 +422,10 @@ __global__ __launch_bounds__(CT) void k_bd_scatter(const uint64_t* __restrict__ 
                                                      uint32_t* __restrict__ bkt,
                                                      void* __restrict__ rec,
                                                      const uint32_t* __restrict__ wfin,
-                                                     int xcd, uint64_t* __restrict__ skeys = nullptr,
+                                                     uint64_t* __restrict__ skeys = nullptr,
                                                      uint32_t* __restrict__ spj = nullptr) {
   extern __shared__ unsigned int cur[];
-  // XCD-aware chunk order (xcd != 0): blocks b and b + 8 share an XCD, so
-  // they get ADJACENT chunks — a bucket's runs are laid out chunk after chunk,
-  // and the line two neighbouring runs share is then written by one L2 and
-  // merged there instead of leaving two partial lines for the fabric
-  int c = blockIdx.x;
-  if (xcd) {
-    const int g = (int)gridDim.x, x = c & 7;
-    c = x * (g >> 3) + min(x, g & 7) + (c >> 3);
-  }
+  const int c = blockIdx.x;
   // keys of 32 bits: 4-byte keys (RW 3 only)
   const bool narrow = RW == 3 && wfin && *wfin == 0u;
   uint32_t* rk32 = reinterpret_cast<uint32_t*>(rec);
@@ -526,7 +499,7 @@ __global__ __launch_bounds__(1024) void k_bd_scatter_s(const uint64_t* __restric
                                                        uint32_t* __restrict__ bkt,
                                                        uint32_t* __restrict__ rec,
                                                        const uint32_t* __restrict__ wfin,
-                                                       int xcd, uint64_t* __restrict__ skeys,
+                                                       uint64_t* __restrict__ skeys,
                                                        uint32_t* __restrict__ spj,
                                                        uint32_t* __restrict__ pj) {
   constexpr int CT = 1024;
@@ -537,11 +510,7 @@ __global__ __launch_bounds__(1024) void k_bd_scatter_s(const uint64_t* __restric
   __shared__ unsigned int wsum[16];
   __shared__ unsigned int tot;
   const int t = threadIdx.x;
-  int c = blockIdx.x;
-  if (xcd) {
-    const int g = (int)gridDim.x, x = c & 7;
-    c = x * (g >> 3) + min(x, g & 7) + (c >> 3);
-  }
+  const int c = blockIdx.x;
   const bool narrow = wfin && *wfin == 0u;
   // 8-byte records: (key, sample) in two arrays of T; 12-byte: three of T
   const int T = narrow ? KT * CT : (KT / 2) * CT;
@@ -897,8 +866,7 @@ __global__ __launch_bounds__(RT) void k_bd_reduce(const uint32_t* __restrict__ b
                                                     float* __restrict__ lacc = nullptr,
                                                     float* __restrict__ lacc_out = nullptr,
                                                     int lacc_n = 0,
-                                                    const uint64_t* __restrict__ bkeys = nullptr,
-                                                    int dbg = 0) {
+                                                    const uint64_t* __restrict__ bkeys = nullptr) {
   __shared__ float acc[kBdTS];
   const int b = blockIdx.x;
   // the step's loss accumulator (added by the forward, ordered before this
@@ -924,7 +892,7 @@ __global__ __launch_bounds__(RT) void k_bd_reduce(const uint32_t* __restrict__ b
     }
 #pragma unroll
     for (int r = 0; r < OCC; ++r) {
-      g[r] = l[r] != kBdInvalid ? ((dbg & 2) ? 1.f : self.grad(gs, j[r], (uint32_t)F)) : 0.f;
+      g[r] = l[r] != kBdInvalid ? self.grad(gs, j[r], (uint32_t)F) : 0.f;
       if (xval && l[r] != kBdInvalid) g[r] *= xval[j[r]];
     }
     // keys occurring once in the batch (usingle, from the dedup): a plain
@@ -932,7 +900,7 @@ __global__ __launch_bounds__(RT) void k_bd_reduce(const uint32_t* __restrict__ b
 #pragma unroll
     for (int r = 0; r < OCC; ++r) {
       if (l[r] == kBdInvalid) continue;
-      if ((dbg & 1) || (usingle && !(dbg & 8) && usingle[ubase[b] + l[r]]))
+      if (usingle && usingle[ubase[b] + l[r]])
         acc[l[r]] = g[r];
       else
         atomicAdd(&acc[l[r]], g[r]);
@@ -967,7 +935,7 @@ __global__ __launch_bounds__(RT) void k_bd_reduce(const uint32_t* __restrict__ b
 #pragma unroll
       for (int r = 0; r < OCC; ++r) {
         const uint32_t l = l0 + r * RT;
-        if (sl[r] < 0 || (dbg & 4)) continue;
+        if (sl[r] < 0) continue;
         if (!snap) wh[r] = *reinterpret_cast<const float2*>(slot_row(t, sl[r]));
         float s2 = 0.f;
         opt_update(op, wh[r].x, wh[r].y, s2, acc[l]);
@@ -1005,35 +973,21 @@ static int bd_rt() {
 }
 // one launch of k_bd_reduce over P buckets at the (SS_BD_RT, SS_BD_ROCC)
 // shape: (1024, 2 / 4), (512, 2 / 4 / 8), (256, 2); others fall back to (1024, 4)
-// SS_BD_DBG (measurement only; wrong results): 1 = plain LDS stores for
-// every occurrence, 2 = no gradient gather, 4 = no table stores, 8 = atomics
-// for single-occurrence keys too
-static int bd_dbg() {
-  static const int v = [] {
-    const char* e = std::getenv("SS_BD_DBG");
-    const int d = e ? std::atoi(e) : 0;
-    if (d)
-      std::fprintf(stderr, "swiftsnails_amd: SS_BD_DBG=%d — k_bd_reduce runs a timing-only "
-                           "variant, training results are WRONG\n", d);
-    return d;
-  }();
-  return v;
-}
 template <typename... A>
 static void bd_reduce_launch(int P, hipStream_t st, A... a) {
-  const int rt = bd_rt(), oc = bd_rocc(), dbg = bd_dbg();
+  const int rt = bd_rt(), oc = bd_rocc();
   if (rt == 512 && oc == 8)
-    hipLaunchKernelGGL((k_bd_reduce<512, 8>), dim3(P), dim3(512), 0, st, a..., dbg);
+    hipLaunchKernelGGL((k_bd_reduce<512, 8>), dim3(P), dim3(512), 0, st, a...);
   else if (rt == 512 && oc == 4)
-    hipLaunchKernelGGL((k_bd_reduce<512, 4>), dim3(P), dim3(512), 0, st, a..., dbg);
+    hipLaunchKernelGGL((k_bd_reduce<512, 4>), dim3(P), dim3(512), 0, st, a...);
   else if (rt == 512)
-    hipLaunchKernelGGL((k_bd_reduce<512, 2>), dim3(P), dim3(512), 0, st, a..., dbg);
+    hipLaunchKernelGGL((k_bd_reduce<512, 2>), dim3(P), dim3(512), 0, st, a...);
   else if (rt == 256)
-    hipLaunchKernelGGL((k_bd_reduce<256, 2>), dim3(P), dim3(256), 0, st, a..., dbg);
+    hipLaunchKernelGGL((k_bd_reduce<256, 2>), dim3(P), dim3(256), 0, st, a...);
   else if (oc == 2)
-    hipLaunchKernelGGL((k_bd_reduce<1024, 2>), dim3(P), dim3(1024), 0, st, a..., dbg);
+    hipLaunchKernelGGL((k_bd_reduce<1024, 2>), dim3(P), dim3(1024), 0, st, a...);
   else
-    hipLaunchKernelGGL((k_bd_reduce<1024, 4>), dim3(P), dim3(1024), 0, st, a..., dbg);
+    hipLaunchKernelGGL((k_bd_reduce<1024, 4>), dim3(P), dim3(1024), 0, st, a...);
 }
 
 // K7 for FM rows [w | v_1..v_K]: per unique key u with occurrences in samples
@@ -1273,41 +1227,23 @@ __global__ __launch_bounds__(1024) void k_bd_reduce_fm_sorted(
   }
 }
 
-// grouped record layout: the per-bucket regroup after the scatter (defined
-// with the record-exchange kernels below)
-static constexpr int kRgT = 512;
-__global__ __launch_bounds__(kRgT) void k_rec_group(const uint32_t* __restrict__ rstart,
-                                                    const uint32_t* __restrict__ rnum,
-                                                    const uint64_t* __restrict__ gkeys,
-                                                    const uint32_t* __restrict__ gspj,
-                                                    uint64_t* __restrict__ skeys,
-                                                    uint32_t* __restrict__ spj,
-                                                    uint32_t* __restrict__ pos_of,
-                                                    uint32_t* __restrict__ usub, int msub, int Pd,
-                                                    int rbits);
-
 // ------------------------------------------------------------- launchers
 int launch_bd_dedup(const uint64_t* keys, long long n, RouteSpec rs, long long ucap,
                     uint32_t* scratch, uint32_t* pj, uint32_t* pos_of, uint32_t* bkt,
                     uint32_t* luid, uint64_t* bkeys, unsigned long long* ucount, uint64_t* ukeys,
                     float* ugrad, int gdim, uint32_t* inv, int place, hipStream_t st,
                     unsigned long long* dbg, uint32_t* rec, uint8_t* usingle, int ndest,
-                    long long lay_n, int msub, uint32_t* usub, uint32_t* spj, uint64_t* gkeys,
-                    uint32_t* gspj) {
+                    long long lay_n, int msub, uint32_t* usub, uint32_t* spj) {
   if (rs.nranks < 1 || rs.nranks > kMaxSeg) throw_error("bdedup: bad nranks");
   // spj (record exchange): no dedup — count, column scan into send-segment
   // positions (d * ucap + ...) with the run tables and per-destination
   // counts, then the scatter writes every occurrence's key into ukeys and its
-  // index into spj at that position (the servers dedup what they receive)
-  // grouped records (kBdRecGroup, msub > 1): the scatter writes into the
-  // staging (gkeys, gspj) and k_rec_group moves each bucket's run into the
-  // send segment grouped by the servers' sub-bucket
-  const bool grouped = spj && (ndest & kBdRecGroup) && msub > 1;
+  // index into spj at that position (the servers dedup what they receive,
+  // whole buckets: records have no server sub-buckets)
   if (spj && (!ukeys || !ucount || rs.nranks > kRecMaxDest || !pos_of ||
-              !(ndest & kBdRecLayout) || (msub != 1 && !grouped) ||
-              (grouped && (!gkeys || !gspj || !usub))))
-    throw_error("bdedup: the record exchange needs ukeys, ucount, pos_of, <= 64 ranks and the "
-                "record layout; sub-buckets only grouped (with the staging and offsets)");
+              !(ndest & kBdRecLayout) || msub != 1))
+    throw_error("bdedup: the record exchange needs ukeys, ucount, pos_of, <= 64 ranks, the "
+                "record layout and no server sub-buckets (msub = 1)");
   if (rs.rbits < 0 || rs.rbits > 20) throw_error("bdedup: region bits 0..20");
   if (msub < 1 || msub > kBdMaxSub || (msub > 1 && !usub))
     throw_error("bdedup: server sub-buckets 1..64 (and their offset table)");
@@ -1429,8 +1365,7 @@ int launch_bd_dedup(const uint64_t* keys, long long n, RouteSpec rs, long long u
     (void)attr;                                                                                   \
     hipLaunchKernelGGL(k_bd_scatter_s<KT>, dim3(L.nch), dim3(1024), s_lds(KT), st, keys, n, rs,  \
                        L.Pd, L.P, L.chunk, S + L.hist, S + L.bstart, pos_of, bkt, rec, wfin,      \
-                       bd_xcd(), spj ? (grouped ? gkeys : ukeys) : nullptr,                       \
-                       grouped ? gspj : spj, pj);                                                 \
+                       spj ? ukeys : nullptr, spj, pj);                                           \
   } break;
       SS_BD_S_CASE(16)
       SS_BD_S_CASE(8)
@@ -1440,16 +1375,10 @@ int launch_bd_dedup(const uint64_t* keys, long long n, RouteSpec rs, long long u
     }
   } else
     SS_BD_CT_DISPATCH2(ct, 3, k_bd_scatter, keys, n, rs, L.Pd, L.P, L.chunk, S + L.hist,
-                       S + L.bstart, pj, pos_of, bkt, rec, wfin,
-                       bd_xcd(), spj ? (grouped ? gkeys : ukeys) : nullptr, grouped ? gspj : spj)
+                       S + L.bstart, pj, pos_of, bkt, rec, wfin, spj ? ukeys : nullptr, spj)
 #undef SS_BD_CT_DISPATCH
 #undef SS_BD_CT_DISPATCH2
   check_launch("k_bd_scatter");
-  if (grouped) {
-    hipLaunchKernelGGL(k_rec_group, dim3(L.P), dim3(kRgT), 0, st, S + L.ubase, S + L.unum, gkeys,
-                       gspj, ukeys, spj, pos_of, usub, msub, L.Pd, rs.rbits);
-    check_launch("k_rec_group");
-  }
   if (spj) return rs.rbits;  // record exchange: the servers dedup
   // place: unique keys straight into the per-destination send segments
   // (+ zeroed gradient rows), reserved with one atomic per bucket
@@ -1490,118 +1419,6 @@ __device__ __forceinline__ void rec_ranges(const unsigned long long* __restrict_
     cs[nd] = a;
   }
   __syncthreads();
-}
-// grouped record layout (kBdRecGroup, N>1 with server sub-buckets): one
-// workgroup per bucket b moves its run [ubase[b], ubase[b] + unum[b]) from the
-// scatter's staging (gkeys, gspj: the same send-segment positions) into the
-// send segment grouped by the server's sub-bucket — the split the unique
-// dedup makes of its keys (region-based with region buckets, so a server
-// sub-bucket is whole regions and its pull can claim) — writing the groups'
-// offsets into usub and every record's final position into pos_of (the
-// scatter wrote the staging positions, and kBdInvalid for empty keys, first)
-__global__ __launch_bounds__(kRgT) void k_rec_group(const uint32_t* __restrict__ rstart,
-                                                    const uint32_t* __restrict__ rnum,
-                                                    const uint64_t* __restrict__ gkeys,
-                                                    const uint32_t* __restrict__ gspj,
-                                                    uint64_t* __restrict__ skeys,
-                                                    uint32_t* __restrict__ spj,
-                                                    uint32_t* __restrict__ pos_of,
-                                                    uint32_t* __restrict__ usub, int msub, int Pd,
-                                                    int rbits) {
-  __shared__ unsigned int cnt[kBdMaxSub];
-  __shared__ unsigned int cur[kBdMaxSub];
-  const int t = threadIdx.x, b = blockIdx.x;
-  // the bucket's run from the run tables the column scan wrote: in the
-  // gapped record layout bstart[b + 1] of a destination's last bucket is the
-  // next destination's first, d * gap away — past the run, into staging the
-  // scatter never wrote
-  const uint32_t p0 = rstart[b], p1 = p0 + rnum[b];
-  if (t < msub) cnt[t] = 0u;
-  __syncthreads();
-  auto sub_of = [&](uint64_t v) -> uint32_t {
-    if (rbits) {
-      const uint64_t region = table_hash(v) >> (64 - rbits);
-      const uint32_t f = (uint32_t)((region * (uint64_t)Pd * (uint64_t)msub) >> rbits);
-      return f - (uint32_t)(b % Pd) * (uint32_t)msub;
-    }
-    return srv_sub(v, msub);
-  };
-  // a wave's lanes grouped by sub-bucket without same-address LDS atomics:
-  // a Zipf-hot key puts thousands of a bucket's records into one sub-bucket,
-  // and one returning LDS atomic per record on that counter serialised them
-  // (9 ms per call at 2 ranks).  Per distinct sub-bucket g of the wave (a
-  // leader lane's, found by ballot): one atomic adds the lanes that share it,
-  // each lane's rank among them is the popcount of the lower matching lanes
-  const int lane = (int)(threadIdx.x & 63);
-  auto wave_slot = [&](bool valid, uint32_t g, unsigned int* ctr, bool ret) -> uint32_t {
-    uint64_t todo = __ballot(valid);
-    uint32_t mine = 0u;
-    while (todo) {
-      const int leader = __ffsll((unsigned long long)todo) - 1;
-      const uint32_t gl = __shfl(g, leader, 64);
-      const uint64_t mask = __ballot(valid && g == gl);
-      uint32_t base = 0u;
-      if (lane == leader) {
-        const unsigned int c = (unsigned int)__popcll(mask);
-        base = ret ? atomicAdd(&ctr[gl], c) : (atomicAdd(&ctr[gl], c), 0u);
-      }
-      base = __shfl(base, leader, 64);
-      if (valid && g == gl)
-        mine = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-      todo &= ~mask;
-    }
-    return mine;
-  };
-  // pass 1: records per sub-bucket (4 per thread in flight); the loop is
-  // wave-uniform (every lane runs the ballots)
-  const uint32_t n = p1 - p0;
-  const uint32_t nr = (n + kRgT - 1) / kRgT;  // rounds of one record per thread
-  for (uint32_t r0 = 0; r0 < nr; r0 += 4) {
-    uint64_t k[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const uint32_t p = p0 + (r0 + r) * kRgT + t;
-      k[r] = (r0 + r < nr && p < p1) ? gkeys[p] : kEmptyKey;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const bool v = k[r] != kEmptyKey;
-      wave_slot(v, v ? min(sub_of(k[r]), (uint32_t)msub - 1) : 0u, cnt, false);
-    }
-  }
-  __syncthreads();
-  if (t == 0) {
-    unsigned int e = 0;
-    for (int i = 0; i < msub; ++i) {
-      cur[i] = e;
-      usub[(long long)b * msub + i] = e;
-      e += cnt[i];
-    }
-  }
-  __syncthreads();
-  // pass 2: every record to its group (the run is re-read from L2)
-  for (uint32_t r0 = 0; r0 < nr; r0 += 4) {
-    uint64_t k[4];
-    uint32_t j[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const uint32_t p = p0 + (r0 + r) * kRgT + t;
-      const bool in = r0 + r < nr && p < p1;
-      k[r] = in ? gkeys[p] : kEmptyKey;
-      j[r] = in ? gspj[p] : kBdInvalid;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const bool v = j[r] != kBdInvalid;
-      const uint32_t g = v && k[r] != kEmptyKey ? min(sub_of(k[r]), (uint32_t)msub - 1) : 0u;
-      const uint32_t q = p0 + wave_slot(v, g, cur, true);
-      if (v) {
-        skeys[q] = k[r];
-        spj[q] = j[r];
-        pos_of[j[r]] = q;
-      }
-    }
-  }
 }
 
 __device__ __forceinline__ long long rec_pos(const long long* cs, int nd, long long gap,

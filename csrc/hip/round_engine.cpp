@@ -124,15 +124,14 @@ class RoundEngine {
   // the stages read what they receive (keys, runs, gradient rows) there.
   // rvals: the response rows the vals put sends.  A rank with a shard adds
   // srv_err (the server merge's error word), svals (looked-up rows), sgrad
-  // (merged gradient rows a caller applies) and, SS_SRV_STAGE=1, gstage (a
-  // cached copy of the received gradient rows)
+  // (merged gradient rows a caller applies)
   void set_xgmi(std::vector<std::vector<XgmiArena*>> arenas,
                 std::vector<std::vector<long long>> keys,
                 std::vector<std::vector<long long>> vals, std::vector<std::vector<long long>> grads,
                 int nranks, int rank, int Pd, int sub, long long cap, int dim, int bpp,
                 double timeout_s, uintptr_t rvals, uintptr_t srv_err, uintptr_t svals,
-                uintptr_t sgrad, uintptr_t gstage) {
-    if (!rvals || !srv_err != !svals || !srv_err != !sgrad || (gstage && !srv_err))
+                uintptr_t sgrad) {
+    if (!rvals || !srv_err != !svals || !srv_err != !sgrad)
       throw std::invalid_argument("set_xgmi: rvals, and srv_err + svals + sgrad for a shard");
     if ((int)arenas.size() != depth_ || (int)keys.size() != depth_ || (int)vals.size() != depth_ ||
         (int)grads.size() != depth_)
@@ -166,7 +165,6 @@ class RoundEngine {
     srv_err_ = srv_err;
     svals_ = svals;
     sgrad_ = sgrad;
-    gstage_ = gstage;
   }
   // drop the arena pointers (the transport is closing): later N>1 stage
   // calls fail in check_xgmi instead of launching against freed arenas
@@ -390,10 +388,10 @@ class RoundEngine {
     if (!own_grad.empty() && (own_grad.size() != 4 || !own_grad[0] || !own_grad[1] ||
                               own_grad[2] < 1 || !self_bypass() || dim_ != 1))
       throw std::invalid_argument("push_xgmi: own_grad = (gs, spj, F, xval), scalar rows, bypass on");
-    // ... which only the fused scalar merge does, and not out of the staging
-    // buffer: refused before anything of the round is enqueued
-    if (!own_grad.empty() && (gstage_ || !scalar_fused))
-      throw std::invalid_argument("push_xgmi: own_grad needs the fused scalar merge, no staging");
+    // ... which only the fused scalar merge does: refused before anything of
+    // the round is enqueued
+    if (!own_grad.empty() && !scalar_fused)
+      throw std::invalid_argument("push_xgmi: own_grad needs the fused scalar merge");
     check_xgmi();
     std::vector<std::vector<long long>> parts;
     parts.push_back(part(grads, ucount, 0, 4ll * dim_, grads_[slot], cap_, self_bypass()));
@@ -414,22 +412,13 @@ class RoundEngine {
       SrvSlot& S = srv_[slot];
       const int Ps = Pd_ * sub_;
       // every source's gradient rows of the round: the grads mailbox
-      uintptr_t rgrads = ar_[slot][2]->base() + grads_[slot].data;
+      const uintptr_t rgrads = ar_[slot][2]->base() + grads_[slot].data;
       SelfSeg sg = self_seg(grads);  // this rank's own gradient rows, in place
       if (!own_grad.empty()) {
         sg.ptr = reinterpret_cast<char*>(own_grad[0]);
         sg.ind = Pt<const uint32_t>(own_grad[1]);
         sg.F = (uint32_t)own_grad[2];
         sg.xv = Pt<const float>(own_grad[3]);
-      }
-      // the peers' gradient rows streamed out of the uncached mailbox into a
-      // cached buffer first: the merge gathers them per received position
-      if (gstage_ && nranks_ > 1) {
-        launch_xstage(Pt<const char>(rgrads),
-                      Pt<const long long>(ar_[slot][2]->base() + grads_[slot].hdr), nranks_,
-                      grads_[slot].seg, 4 * dim_, sg.ptr ? rank_ : -1, Pt<char>(gstage_),
-                      St(stream));
-        rgrads = gstage_;
       }
       if (srv_s32_[slot] && !(update && scalar_fused && snap))
         throw std::logic_error("push_xgmi: a 4-byte-slot pull needs the fused snapshot merge");
@@ -566,8 +555,8 @@ class RoundEngine {
   std::vector<SrvSlot> srv_;
   std::vector<LocalSlot> local_;
   // N>1, for the engine's life: response rows out; a shard's error word,
-  // looked-up rows, merged gradient rows and gradient staging (0: none)
-  uintptr_t rvals_ = 0, srv_err_ = 0, svals_ = 0, sgrad_ = 0, gstage_ = 0;
+  // looked-up rows and merged gradient rows (0: none)
+  uintptr_t rvals_ = 0, srv_err_ = 0, svals_ = 0, sgrad_ = 0;
   std::vector<std::array<XgmiArena*, 3>> ar_;  // per slot: keys, vals, grads
   std::vector<std::array<XReg, 4>> keys_;
   int nkp_ = 3;  // parts of the keys channel
@@ -613,8 +602,7 @@ void bind_round_engine(py::module_& m) {
       // owns this object
       .def("set_xgmi", &RoundEngine::set_xgmi, py::keep_alive<1, 2>(), py::kw_only(), "arenas"_a,
            "keys"_a, "vals"_a, "grads"_a, "nranks"_a, "rank"_a, "Pd"_a, "sub"_a, "cap"_a, "dim"_a,
-           "bpp"_a, "timeout_s"_a, "rvals"_a, "srv_err"_a = 0, "svals"_a = 0, "sgrad"_a = 0,
-           "gstage"_a = 0)
+           "bpp"_a, "timeout_s"_a, "rvals"_a, "srv_err"_a = 0, "svals"_a = 0, "sgrad"_a = 0)
       .def("clear_xgmi", &RoundEngine::clear_xgmi)
       .def("set_server_slot", &RoundEngine::set_server_slot, "slot"_a, py::kw_only(), "cnt"_a,
            "bstart"_a, "ubase"_a, "unum"_a, "pj"_a, "luid"_a, "bkeys"_a, "slots"_a, "ucount"_a,

@@ -99,9 +99,6 @@ void launch_xwait(char* arena, const XWait& W, unsigned long long* waited, unsig
                   hipStream_t st);
 // litmus patterns: word i of a segment = mix(seed, i); check counts mismatches
 void launch_xpattern(int* dst, long long words, unsigned seed, hipStream_t st);
-// received rows out of the uncached mailbox into a cached buffer (k_xstage)
-void launch_xstage(const char* src, const long long* cnt, int nsrc, long long seg_bytes,
-                   int row_bytes, int skip, char* dst, hipStream_t st);
 void launch_xcheck(const int* src, long long words, unsigned seed, int* bad, hipStream_t st);
 void launch_spin(double us, hipStream_t st);
 
@@ -123,17 +120,8 @@ class XgmiArena {
     if (bytes < kXHeadBytes) throw_error("xgmi: arena smaller than its flag and tag area");
     check_hip(hipSetDevice(device), "hipSetDevice");
     void* p = nullptr;
-    // SS_XGMI_CACHED=1 (measurement only, one-rank arenas): an ordinary
-    // cached allocation — what the uncached mailbox costs its local readers
-    static const bool cached = [] {
-      const char* e = std::getenv("SS_XGMI_CACHED");
-      return e && e[0] == '1';
-    }();
-    if (cached && nranks == 1)
-      check_hip(hipMalloc(&p, (size_t)bytes), "xgmi arena (cached, one rank)");
-    else
-      check_hip(hipExtMallocWithFlags(&p, (size_t)bytes, hipDeviceMallocUncached),
-                "xgmi arena (uncached)");
+    check_hip(hipExtMallocWithFlags(&p, (size_t)bytes, hipDeviceMallocUncached),
+              "xgmi arena (uncached)");
     base_ = static_cast<char*>(p);
     check_hip(hipMemset(base_, 0, (size_t)kXHeadBytes), "xgmi flags");
     check_hip(hipMalloc(&local_, sizeof(unsigned long long) * kXLocalWords), "xgmi counters");

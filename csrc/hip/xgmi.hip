@@ -224,39 +224,6 @@ __device__ __forceinline__ int xpattern_word(unsigned seed, long long i) {
   return (int)x;
 }
 
-// Received segments out of the (uncached) mailbox into a cached buffer at
-// the same offsets: source s's first cnt[s] rows of row_bytes each, at byte
-// s * seg_bytes, streamed with 16-byte accesses (every source but `skip`, the
-// rank's own segment, which its consumer reads in place).  The server's
-// gradient merge then gathers per received position from L2 / MALL instead
-// of one uncached memory transaction per 4-byte gather.
-__global__ __launch_bounds__(256) void k_xstage(const char* __restrict__ src,
-                                                const long long* __restrict__ cnt,
-                                                long long seg_bytes, int row_bytes, int skip,
-                                                char* __restrict__ dst) {
-  const int s = blockIdx.y;
-  if (s == skip) return;  // block-uniform
-  const long long n = cnt[s] * (long long)row_bytes;
-  const long long nv = n / 16;
-  const uint4* sv = reinterpret_cast<const uint4*>(src + s * seg_bytes);
-  uint4* dv = reinterpret_cast<uint4*>(dst + s * seg_bytes);
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nv;
-       i += (long long)gridDim.x * 256)
-    dv[i] = sv[i];
-  const long long tail = n - nv * 16;  // whole 4-byte words (row_bytes % 4 == 0)
-  if (blockIdx.x == 0 && threadIdx.x < tail / 4)
-    reinterpret_cast<uint32_t*>(dst + s * seg_bytes + nv * 16)[threadIdx.x] =
-        reinterpret_cast<const uint32_t*>(src + s * seg_bytes + nv * 16)[threadIdx.x];
-}
-
-void launch_xstage(const char* src, const long long* cnt, int nsrc, long long seg_bytes,
-                   int row_bytes, int skip, char* dst, hipStream_t st) {
-  if (nsrc < 1 || row_bytes % 4 || seg_bytes % 16) throw_error("xstage: layout");
-  hipLaunchKernelGGL(k_xstage, dim3(128, nsrc), dim3(256), 0, st, src, cnt, seg_bytes, row_bytes,
-                     skip, dst);
-  check_launch("k_xstage");
-}
-
 __global__ __launch_bounds__(256) void k_xpattern(int* dst, long long words, unsigned seed) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < words;
        i += (long long)gridDim.x * 256)
@@ -408,29 +375,6 @@ void bind_xgmi(py::module_& m) {
   m.def("spin_us", [](double us, uintptr_t st) {
     ss::launch_spin(us, reinterpret_cast<hipStream_t>(st));
   });
-  // a stream whose kernels run on `ncus` of the device's CUs only (spread
-  // evenly over the CU ids, so every XCD keeps some): the route stream's
-  // dedup kernels then leave the other CUs to the main stream's
-  // latency-bound table kernels (SS_ROUTE_CUS).  `priority`: the stream's
-  // priority (hipStreamCreateWithPriority semantics; 0 = default).  Never
-  // destroyed: it lives as long as the engine that wraps it.
-  m.def("cu_stream", [](int device, int ncus, int invert) {
-    ss::check_hip(hipSetDevice(device), "hipSetDevice");
-    int total = 0;
-    ss::check_hip(hipDeviceGetAttribute(&total, hipDeviceAttributeMultiprocessorCount, device),
-                  "CU count");
-    if (ncus < 1 || ncus > total) throw std::invalid_argument("cu_stream: 1..CU count CUs");
-    std::vector<uint32_t> mask((total + 31) / 32, invert ? 0xFFFFFFFFu : 0u);
-    for (int k = 0; k < ncus; ++k) {
-      const int cu = (int)((long long)k * total / ncus);
-      if (invert) mask[cu / 32] &= ~(1u << (cu % 32));
-      else mask[cu / 32] |= 1u << (cu % 32);
-    }
-    hipStream_t st = nullptr;
-    ss::check_hip(hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data()),
-                  "hipExtStreamCreateWithCUMask");
-    return reinterpret_cast<uintptr_t>(st);
-  }, py::arg("device"), py::arg("ncus"), py::arg("invert") = 0);
   m.def("device_pci_id", [](int device) {
     char buf[64] = {0};
     ss::check_hip(hipDeviceGetPCIBusId(buf, sizeof(buf), device), "hipDeviceGetPCIBusId");

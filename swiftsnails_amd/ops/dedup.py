@@ -61,8 +61,7 @@ class Deduper:
 
     def __init__(self, max_n: int, nranks: int = 1, frag_map: Optional[torch.Tensor] = None,
                  gdim: int = 1, device=None, with_grad: bool = True, zero_grad: bool = True,
-                 mode: Optional[str] = None, record_layout: bool = False,
-                 record_group: bool = False):
+                 mode: Optional[str] = None, record_layout: bool = False):
         from .._native import hip
 
         self.mode = mode or os.environ.get("SS_DEDUP", "bucket")
@@ -124,14 +123,8 @@ class Deduper:
         # enable_records) the record-layout bit — smaller source buckets, so
         # that N sources' records fill one server bucket (bdedup.hip)
         self.record_layout = bool(record_layout)
-        # ... record_group (N>1): the unique layout's fuller source buckets,
-        # each bucket's records then grouped by the servers' sub-bucket after
-        # the scatter (bdedup.hip k_rec_group; split_for_servers(m > 1))
-        self.record_group = bool(record_layout and record_group)
         self.ndest = effective_ndest(frag_map, self.nranks) | (
-            self.h.bd_record_layout_bit() if self.record_layout else 0) | (
-            self.h.bd_record_group_bit() if self.record_group else 0)
-        self.gkeys = self.gspj = None  # grouped records: the scatter's staging
+            self.h.bd_record_layout_bit() if self.record_layout else 0)
         self.frag_map = frag_map.to(d, torch.int32).contiguous()
         m = max(1, self.max_n)
         if self.mode == "bucket" and m > self.h.bd_max_keys():
@@ -191,9 +184,7 @@ class Deduper:
                             self.usingle.data_ptr() if self.usingle is not None else 0,
                             self.ndest, self.lay_n or 0, self.msub,
                             self.usub.data_ptr() if self.usub is not None else 0,
-                            self.rbits, self.spj.data_ptr() if self.spj is not None else 0,
-                            self.gkeys.data_ptr() if self.gkeys is not None else 0,
-                            self.gspj.data_ptr() if self.gspj is not None else 0)
+                            self.rbits, self.spj.data_ptr() if self.spj is not None else 0)
             return DedupResult(self.ukeys, self.ucount, self.inv[:n], self.ugrad, self.ucap,
                                self.nranks, n, self, self._lay(n), int(used or 0))
         # the scratch is all-EMPTY between calls: the finish kernel resets the
@@ -228,10 +219,14 @@ class Deduper:
     def split_for_servers(self, m: int) -> None:
         """Group each bucket's unique keys by the servers' sub-bucket (one
         of ``m``, server.hip) and record the groups' offsets (bucket mode,
-        N>1 engines with a fixed ``lay_n``)."""
+        N>1 engines with a fixed ``lay_n``; not the record layout, whose
+        servers dedup whole buckets)."""
         if m <= 1:
             self.msub, self.usub = 1, None
             return
+        if self.record_layout:
+            raise RuntimeError("split_for_servers: the record layout has no server "
+                               "sub-buckets (m = 1)")
         if self.mode != "bucket" or not self.lay_n:
             raise RuntimeError("split_for_servers needs mode='bucket' and lay_n")
         P = self.h.bd_buckets(self.lay_n, self.nranks, self.ndest)
@@ -247,23 +242,16 @@ class Deduper:
 
     def enable_records(self) -> None:
         """Route every occurrence instead of the unique keys (bucket mode,
-        N>1 engines with a fixed ``lay_n``; sub-buckets with record_group,
-        each bucket's records grouped by them): ukeys holds the
-        occurrences' keys at their send-segment positions, ``spj`` their
+        N>1 engines with a fixed ``lay_n``, no server sub-buckets): ukeys
+        holds the occurrences' keys at their send-segment positions, ``spj`` their
         occurrence indices, ``ucount`` the records per destination, and the
         run tables the records per bucket (the servers dedup them)."""
-        if self.mode != "bucket" or not self.lay_n or not self.record_layout or (
-                self.msub != 1 and not self.record_group):
-            raise RuntimeError("enable_records needs mode='bucket', lay_n and "
-                               "Deduper(record_layout=True); sub-buckets only with record_group")
+        if self.mode != "bucket" or not self.lay_n or not self.record_layout or self.msub != 1:
+            raise RuntimeError("enable_records needs mode='bucket', lay_n, "
+                               "Deduper(record_layout=True) and no server sub-buckets")
         if self.spj is None:
             self.spj = torch.empty(self.nranks * self.ucap, dtype=torch.int32,
                                    device=self.device)
-        if self.msub > 1 and self.gkeys is None:
-            self.gkeys = torch.empty(self.nranks * self.ucap, dtype=torch.int64,
-                                     device=self.device)
-            self.gspj = torch.empty(self.nranks * self.ucap, dtype=torch.int32,
-                                    device=self.device)
         self.need_pos = True
         self.need_bkt = False
         self.materialize_inv = False

@@ -198,16 +198,7 @@ class PSEngine(HostRounds, DeviceSetup, EngineControl):
         self.tracer = Tracer(enabled=False)
         fm = torch.from_numpy(self.frag_map.astype(np.int32))
         dd_cls = Deduper if self.gpu else CpuDeduper
-        # N>1 records, SS_REC_GROUP=1: the unique layout's source buckets,
-        # each bucket's records grouped by the servers' sub-bucket after the
-        # scatter (bdedup.hip k_rec_group).  Measured slower than the small
-        # record buckets (3584 / N records, no sub-buckets; default): 2 ranks
-        # on one GPU 2.18 vs 1.75 ms, 4 ranks 4.54 vs 3.96, 8 ranks 8.83 vs
-        # 8.86 (profiles/raw/r6_rec_group_ab.txt) — the regroup's per-record
-        # pos_of stores land in random order
-        self.rec_group = bool(self.records and self.world > 1 and
-                              os.environ.get("SS_REC_GROUP", "0") == "1")
-        rl = {"record_layout": True, "record_group": self.rec_group} if self.records else {}
+        rl = {"record_layout": True} if self.records else {}
         self.dedupers = [dd_cls(self.max_keys, nranks=self.world, frag_map=fm, gdim=self.dim,
                                 device=self.device, zero_grad=zero_grad, **rl)
                          for _ in range(self.depth)]
@@ -228,12 +219,12 @@ class PSEngine(HostRounds, DeviceSetup, EngineControl):
         self.slot32, self.slots, self._snaps = False, None, None
         self.Pd, self.sub, self.Ps, self.srv_rbits = 0, 1, 0, 0
         self.lookup_slot = self._lk_dd = self.rvals = None
-        self.srv = self.srv_err = self.svals = self.sgrad = self.gstage = self.own_vals = None
+        self.srv = self.srv_err = self.svals = self.sgrad = self.own_vals = None
         self.srv_ahead, self._route_srv = False, None  # _route_srv: how the last route ran
         self.server_stream = self._server_stream_off = None
         if self.gpu:
             self.route_stream = (streams_of.route_stream if streams_of is not None
-                                 else self._make_route_stream(dev))
+                                 else torch.cuda.Stream(device=dev))
             # + one slot past the ring: the N>1 read-only lookup's round
             # (PSEngine.lookup) never touches a ring slot the pipeline holds
             self.native = _hip().RoundEngine(self.depth + 1, self._dix)
@@ -314,16 +305,6 @@ class PSEngine(HostRounds, DeviceSetup, EngineControl):
             self.pull_ahead = True
             if self.gpu and not self.shared_device:
                 self.pull_stream = torch.cuda.Stream(device=self.device)
-
-    def _make_route_stream(self, dev) -> torch.cuda.Stream:
-        """The route stream; SS_ROUTE_CUS=n: restricted to n of the device's
-        CUs (a CU-masked HIP stream), so the dedup's large workgroups leave
-        the remaining CUs to the main stream's latency-bound table kernels."""
-        n = int(os.environ.get("SS_ROUTE_CUS", "0") or 0)
-        if n <= 0:
-            return torch.cuda.Stream(device=dev)
-        ptr = _hip().cu_stream(dev.index or 0, n, 0)
-        return torch.cuda.ExternalStream(ptr, device=dev)
 
     def last_route_matches(self) -> bool:
         """The last routed round ran the keys-in as a route issued now would
@@ -603,13 +584,11 @@ class PSEngine(HostRounds, DeviceSetup, EngineControl):
         this rank's own records' rows in the cached ``own_vals`` buffer and
         their gradients read by the server merge straight from the worker's
         per-sample gradient (``Round.own_grad``).  Only the fused merge of
-        scalar two-float rows reads gradients that way, and not through the staging
-        buffer: every other rule (SGD, bf16 rows, a tensor-code push method,
-        SS_SRV_STAGE=1) sends its own records through the arena like the
-        peers'.  Asked per round — by the pull, by the worker's compute and by
+        scalar two-float rows reads gradients that way: every other rule (SGD,
+        bf16 rows, a tensor-code push method) sends its own records through
+        the arena like the peers'.  Asked per round — by the pull, by the worker's compute and by
         the push — since a push method may be installed between rounds."""
-        return (self.own_vals is not None and self._server_update_kind() == "scalar" and
-                self.gstage is None)
+        return self.own_vals is not None and self._server_update_kind() == "scalar"
 
     def _srv_stream(self, host_side: bool) -> int:
         """hipStream_t of the server stream for this stage, 0 for none.  A

@@ -36,9 +36,7 @@ class EngineControl:
             # SS_BD_TARGET_DIST (the N>1 source-bucket target), and the target
             # this layout actually uses (a one-rank layout takes SS_BD_TARGET)
             "bd_target_dist": int(h.bd_target_dist()),
-            "bucket_target": int(h.bd_target_for(self.world,
-                                                 self.records and not self.rec_group)),
-            "record_group": bool(self.rec_group),
+            "bucket_target": int(h.bd_target_for(self.world, self.records)),
             "buckets_per_dest": int(self.Pd),
             "srv_sub_buckets": int(self.sub),
             "claim": bool(self.claim),

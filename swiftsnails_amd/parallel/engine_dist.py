@@ -57,12 +57,9 @@ class DeviceSetup:
             dd.lay_n = cap
         self.Pd = h.bd_buckets(cap, N, self.dedupers[0].ndest) // N
         # record exchange: a server bucket is N runs of records sized for one
-        # LDS table together (bdedup.hip bd_target), no sub-buckets — or, with
-        # grouped records (rec_group), the unique layout's buckets and its
-        # sub-bucket split (the sender groups each run's records by it)
-        bits = h.bd_record_layout_bit() | h.bd_record_group_bit()
-        self.sub = 1 if (self.records and not self.rec_group) else h.srv_sub_buckets(
-            N, cap, self.dedupers[0].ndest & ~bits)
+        # LDS table together (bdedup.hip bd_target), no sub-buckets
+        self.sub = 1 if self.records else h.srv_sub_buckets(
+            N, cap, self.dedupers[0].ndest & ~h.bd_record_layout_bit())
         self.Ps = self.Pd * self.sub
         # sub > 1: every source groups its runs by the servers' sub-bucket
         # and sends the offsets with them (the server reads exact ranges)
@@ -87,8 +84,7 @@ class DeviceSetup:
             from ..ops.dedup import Deduper
 
             lk = Deduper(self.max_keys, nranks=N, frag_map=self.dedupers[0].frag_map.cpu(),
-                         gdim=d, device=dev, record_layout=self.records,
-                         record_group=self.rec_group)
+                         gdim=d, device=dev, record_layout=self.records)
             lk.lay_n = cap
             lk.split_for_servers(self.sub)
             lk.need_ukeys = True
@@ -142,14 +138,6 @@ class DeviceSetup:
         if self.table is not None:
             self.svals = torch.empty((rows, d), dtype=torch.float32, device=dev)
             self.sgrad = torch.empty((rows, d), dtype=torch.float32, device=dev)
-            # SS_SRV_STAGE=1: a cached copy of the received gradient rows (the
-            # mailboxes are uncached; the server merge gathers per received
-            # position), streamed out of the mailbox before the merge.
-            # Measured neutral with 4 and 8 ranks on one GPU (4.14-4.33 vs
-            # 4.17-4.24 ms, 8.23-8.26 vs 8.23-8.37): off by default
-            self.gstage = (torch.empty((rows, d), dtype=torch.float32, device=dev)
-                           if self.xg is not None and N > 1 and
-                           os.environ.get("SS_SRV_STAGE", "0") == "1" else None)
             self.srv_err = torch.zeros(1, dtype=torch.int32, device=dev)
             snap_ok = bool(getattr(self.table, "snapshot_ok", False))
             self.srv = [_ServerSlot(rows, self.Ps, dev, snap_ok and q < self.depth)
@@ -178,8 +166,7 @@ class DeviceSetup:
                 grads=[list(self.xg.layout("grads", 0, q)) for q in range(NS)],
                 nranks=N, rank=self.rank, Pd=self.Pd, sub=self.sub, cap=cap, dim=d,
                 bpp=self.xg.bpp, timeout_s=self.xg.timeout_s, rvals=self.rvals.data_ptr(),
-                srv_err=_ptr(self.srv_err), svals=_ptr(self.svals), sgrad=_ptr(self.sgrad),
-                gstage=_ptr(self.gstage))
+                srv_err=_ptr(self.srv_err), svals=_ptr(self.svals), sgrad=_ptr(self.sgrad))
             # a closed transport frees its arenas: the engine forgets them first
             self.xg._close_hooks.append(self.native.clear_xgmi)
             for q, S in enumerate(self.srv or ()):

@@ -80,9 +80,6 @@ KNOBS: dict[str, Knob] = {
                                  "measures both)"),
     "SS_MAIN_PRIO": Knob("0", "bench.py", "experiment",
                          "1: bench.py runs the step's main stream at the highest stream priority"),
-    "SS_ROUTE_CUS": Knob("0", "parallel/engine.py", "experiment",
-                         "n > 0: the route stream runs on n of the device's CUs (CU-masked "
-                         "stream), leaving the rest to the main stream"),
     "SS_CLAIM_T": Knob("256", "csrc/hip/table.hip", "tuning",
                        "claimed pull: threads per bucket workgroup (256 / 512 / 1024: 0.795 / "
                        "0.833 / 0.843 ms per bench step on one box)"),
@@ -95,16 +92,6 @@ KNOBS: dict[str, Knob] = {
                     "dedup and merge (less kernel work per rank at N <= 2, twice the link "
                     "bytes); auto (bench.py) = both timed on the live world after the "
                     "warm-up, the faster kept (the launcher runs unique)"),
-    "SS_REC_GROUP": Knob("0", "parallel/engine.py", "tuning",
-                         "1: N>1 record exchange with the unique layout's source buckets, each "
-                         "bucket's records grouped by the servers' sub-bucket (measured slower "
-                         "than the default 3584 / N records per source bucket at 2 and 4 ranks)"),
-    "SS_BD_DBG": Knob("0", "csrc/hip/bdedup.hip", "debug",
-                      "measurement only, wrong results: k_bd_reduce bits 1 = plain LDS stores, "
-                      "2 = no gradient gather, 4 = no table stores, 8 = atomics for single keys"),
-    "SS_XGMI_CACHED": Knob("0", "csrc/hip/xgmi.h", "experiment",
-                           "1 (one-rank arenas only): the mailbox arenas as ordinary cached "
-                           "memory — measures what the uncached mailbox costs its local readers"),
     "SS_CAL_XCHG": Knob("", "models/base.py", "debug",
                         "debug: force calibrate_exchange's outcome (unique / records)"),
     "SS_REC_OCC": Knob("own", "parallel/engine_dist.py", "tuning",
@@ -113,10 +100,6 @@ KNOBS: dict[str, Knob] = {
                        "(never written per occurrence) — in rounds the fused scalar AdaGrad "
                        "merge serves, without staging; arena = both through the mailbox, "
                        "like the peers' records (every other rule's rounds always)"),
-    "SS_SRV_STAGE": Knob("0", "parallel/engine_dist.py", "tuning",
-                         "1: N>1 xGMI servers stream the peers' gradient rows out of the "
-                         "uncached mailbox into a cached buffer before the merge gathers them "
-                         "(measured neutral at 4 / 8 ranks on one GPU)"),
     "SS_W2V_FUSE": Knob("1", "models/word2vec.py", "tuning",
                         "one GPU: the word2vec occurrence-row reduce runs the optimizer update "
                         "of single-item keys itself; the apply kernel only the rest (0: reduce, "
@@ -127,9 +110,6 @@ KNOBS: dict[str, Knob] = {
     "SS_BD_NCH": Knob("128", "csrc/hip/bdedup.hip", "tuning",
                       "max count/scatter chunks (1 GPU 512 -> 128: 0.93 -> 0.89 ms/step; "
                       "N>1 path 128 / 256 / 512: 1.06 / 1.03 / 1.05)"),
-    "SS_BD_XCD": Knob("0", "csrc/hip/bdedup.hip", "tuning",
-                      "1: scatter chunks in XCD-aware order (blocks b, b+8 share an XCD and get "
-                      "adjacent chunks; measured neutral)"),
     "SS_BD_SKT": Knob("16", "csrc/hip/bdedup.hip", "tuning",
                       "sorted scatter: largest keys per thread per LDS tile (16 / 8 / 4 / 2; "
                       "halved for 12-byte records and when the bucket table needs the LDS)"),
@@ -167,9 +147,6 @@ KNOBS: dict[str, Knob] = {
     "SS_CLAIM_TS": Knob("8192", "csrc/hip/table.hip", "tuning",
                         "claimed pull: LDS claim-set entries (8192, or 4096: 32 instead of "
                         "48 KB of LDS per workgroup)"),
-    "SS_CLAIM_KR": Knob("1", "csrc/hip/table.hip", "tuning",
-                        "claimed pull: keys per thread whose first probe loads are in flight "
-                        "together (1 / 4 / 8; 4 and 8 measured slower)"),
     "SS_BD_ROCC": Knob("4", "csrc/hip/bdedup.hip", "tuning",
                        "k_bd_reduce: occurrences (and fused-update rows) per thread in flight, "
                        "2 or 4"),

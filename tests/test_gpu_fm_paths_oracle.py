@@ -89,7 +89,7 @@ pytestmark = pytest.mark.gpu
 
 CAP = 1 << 18
 KNOBS = ("SS_CLAIM", "SS_SLOT32", "SS_TABLE_REGIONS", "SS_ENGINE_GENERAL", "SS_DEDUP",
-         "SS_SRV_STAGE", "SS_XGMI_SELF", "SS_SERVER_STREAM", "SS_STALENESS", "SS_ENGINE_DEPTH",
+         "SS_XGMI_SELF", "SS_SERVER_STREAM", "SS_STALENESS", "SS_ENGINE_DEPTH",
          "SS_TABLE_G", "SS_FM_REDUCE", "SS_PULL_STREAM")
 
 

@@ -548,7 +548,7 @@ def test_evict_on_the_derived_weight(dev, cap):
 # ------------------------------------------------------------- engine level
 LR_CAP = 1 << 20
 KNOBS = ("SS_CLAIM", "SS_SLOT32", "SS_TABLE_REGIONS", "SS_ENGINE_GENERAL", "SS_DEDUP",
-         "SS_REC_OCC", "SS_REC_GROUP", "SS_SRV_STAGE", "SS_XGMI_SELF", "SS_SERVER_STREAM",
+         "SS_REC_OCC", "SS_XGMI_SELF", "SS_SERVER_STREAM",
          "SS_STALENESS", "SS_ENGINE_DEPTH", "SS_TABLE_G", "SS_TABLE_PREFILL", "SS_TABLE_LAYOUT")
 
 

@@ -12,7 +12,7 @@ same question — do the engine's rounds compute sparse LR? — is put to
   ``k_rec_grad`` and the server merge's own segment; a quarter of the keys
   need 12-byte route records) and binary features (``binary32``);
 * **AdaGrad and SGD**, a **tensor-code** rule (installed before and after
-  the engine exists), **bf16** rows, and the server's gradient staging;
+  the engine exists) and **bf16** rows;
 * **world 2** (two ranks on one GPU): rank 1's own segment sits at the
   non-zero offset ``rank * cap``.
 
@@ -25,10 +25,9 @@ within the oracle's own first-order tolerance (``tol_w`` / ``tol_h``,
 calibrated on the CPU in ``test_lr_oracle_cpu.py``: no key excused, no
 tolerance tuned to the kernels).
 
-The record rounds with SGD, bf16 rows, a tensor-code rule or
-``SS_SRV_STAGE=1`` used to raise ``push_xgmi: own_grad needs the fused scalar
-merge, no staging`` — after the round's gradient put was enqueued: the engine
-now takes the own-record shortcut only for rounds whose merge can read it
+The record rounds with SGD, bf16 rows or a tensor-code rule used to raise
+``push_xgmi: own_grad needs the fused scalar merge`` — after the round's
+gradient put was enqueued: the engine now takes the own-record shortcut only for rounds whose merge can read it
 (``PSEngine.own_merge``).  Those cases must run, not raise.
 
 Measured on an MI355X, the largest |engine - oracle| / tol per path (w, h;
@@ -36,7 +35,7 @@ each case prints its own as ``MARGIN ...``; reported, not tuned):
 
     fast path            0.062  0.166      records, own      0.055  0.164
     xGMI unique          0.043  0.166      records, arena    0.047  0.167
-    tensor-code rule     0.009  -          world 2 (all 4)   0.009  0.030
+    tensor-code rule     0.009  -          world 2 (all 3)   0.009  0.022
 
 The binary32 / AdaGrad cases set every maximum of h (0.164-0.167, all paths
 alike, and 0.166 for the fp32 NumPy evaluation on the CPU): it is the fp32
@@ -57,8 +56,8 @@ pytestmark = pytest.mark.gpu
 
 CAP = 1 << 22
 KNOBS = ("SS_CLAIM", "SS_SLOT32", "SS_TABLE_REGIONS", "SS_ENGINE_GENERAL", "SS_DEDUP",
-         "SS_REC_OCC", "SS_REC_GROUP", "SS_SRV_STAGE", "SS_XGMI_SELF", "SS_SERVER_STREAM",
-         "SS_STALENESS", "SS_ENGINE_DEPTH", "SS_TABLE_G")
+         "SS_REC_OCC", "SS_XGMI_SELF", "SS_SERVER_STREAM", "SS_STALENESS", "SS_ENGINE_DEPTH",
+         "SS_TABLE_G")
 PATHS = ("fast", "unique", "records_own", "records_arena")
 
 
@@ -249,13 +248,11 @@ def test_records_own_bf16_rows(dev, files, monkeypatch):
 
 
 # ------------------------------------------------------------------ world 2
-def _rank(rank, world, path, name, optimizer, exchange, stage, init, q):
+def _rank(rank, world, path, name, optimizer, exchange, init, q):
     os.environ["SS_PULL_AHEAD"] = "0"
     os.environ["SS_XGMI_TIMEOUT"] = "30"
-    os.environ["SS_SRV_STAGE"] = "1" if stage else "0"
     for k in KNOBS:
-        if k != "SS_SRV_STAGE":
-            os.environ.pop(k, None)
+        os.environ.pop(k, None)
     init_gloo(init, rank, world)
     try:
         from swiftsnails_amd.models.sparse_lr import SparseLRWorker
@@ -273,8 +270,7 @@ def _rank(rank, world, path, name, optimizer, exchange, stage, init, q):
         src = _source(path, name, O.B // world, dev, rank, world)
         w = SparseLRWorker(eng, src, rank=rank, world=world)
         flags = {"records": bool(eng.records), "own": bool(eng.own_merge()),
-                 "gring": w.gring is not None, "stage": eng.gstage is not None,
-                 "xval": w.xval is not None}
+                 "gring": w.gring is not None, "xval": w.xval is not None}
         losses = _train(w)
         eng.check()
         table.check()
@@ -284,13 +280,12 @@ def _rank(rank, world, path, name, optimizer, exchange, stage, init, q):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("exchange,optimizer,stage", [
-    ("records", "adagrad", False),   # rank 1's own segment at a non-zero offset
-    ("unique", "adagrad", False),
-    ("records", "sgd", False),
-    ("records", "adagrad", True),    # SS_SRV_STAGE=1
+@pytest.mark.parametrize("exchange,optimizer", [
+    ("records", "adagrad"),   # rank 1's own segment at a non-zero offset
+    ("unique", "adagrad"),
+    ("records", "sgd"),
 ])
-def test_lr_world2_matches_fp64_oracle(files, exchange, optimizer, stage):
+def test_lr_world2_matches_fp64_oracle(files, exchange, optimizer):
     """Two ranks on one GPU, each reading its half of the file: a synchronous
     round is one update per key on the sum of both ranks' gradients, the
     world-1 update of the union batch."""
@@ -299,7 +294,7 @@ def test_lr_world2_matches_fp64_oracle(files, exchange, optimizer, stage):
     q = ctx.Queue()
     init = file_init()
     procs = [ctx.Process(target=_rank, args=(r, world, files[name], name, optimizer, exchange,
-                                             stage, init, q)) for r in range(world)]
+                                             init, q)) for r in range(world)]
     for p in procs:
         p.start()
     res = collect(q, procs, world, 120)
@@ -309,13 +304,12 @@ def test_lr_world2_matches_fp64_oracle(files, exchange, optimizer, stage):
     res.sort(key=lambda x: x[0])
     ada = optimizer == "adagrad"
     for _, _, _, _, f in res:
-        assert f["xval"] and f["records"] == (exchange == "records") and f["stage"] == stage
-        # the AdaGrad fp32 default keeps the own-record path; staging and SGD leave it
-        assert f["own"] == (exchange == "records" and ada and not stage)
+        assert f["xval"] and f["records"] == (exchange == "records")
+        # the AdaGrad fp32 default keeps the own-record path; SGD leaves it
+        assert f["own"] == (exchange == "records" and ada)
         assert f["gring"] or not f["own"]
     keys = np.concatenate([x[2] for x in res])
     rows = np.concatenate([x[3] for x in res])
     assert all(len(x[2]) > 0 for x in res)  # both shards hold keys
-    _check(f"world2 {exchange} {optimizer}{' staged' if stage else ''}",
-           O.reference(name, optimizer, world), [x[1] for x in res], keys, rows, world=world,
-           with_h=ada)
+    _check(f"world2 {exchange} {optimizer}", O.reference(name, optimizer, world),
+           [x[1] for x in res], keys, rows, world=world, with_h=ada)

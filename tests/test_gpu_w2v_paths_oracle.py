@@ -87,7 +87,7 @@ pytestmark = pytest.mark.gpu
 
 STEPS = O.STEPS
 KNOBS = ("SS_CLAIM", "SS_SLOT32", "SS_TABLE_REGIONS", "SS_ENGINE_GENERAL", "SS_DEDUP",
-         "SS_SRV_STAGE", "SS_XGMI_SELF", "SS_SERVER_STREAM", "SS_STALENESS", "SS_ENGINE_DEPTH",
+         "SS_XGMI_SELF", "SS_SERVER_STREAM", "SS_STALENESS", "SS_ENGINE_DEPTH",
          "SS_TABLE_G", "SS_PULL_STREAM", "SS_W2V_FUSE", "SS_W2V_MFMA", "SS_W2V_PP_ITEMS",
          "SS_W2V_PP_QF", "SS_W2V_PP_STAGES", "SS_W2V_EARLY_SLOT", "SS_W2V_WIN_GRID",
          "SS_BD_TARGET", "SS_PULL_VEC", "SS_GRAPH")

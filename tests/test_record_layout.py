@@ -43,20 +43,44 @@ def test_unique_layout_unchanged_by_the_bit():
         assert world * (N_BENCH / P) * 1.25 / m <= 3000  # <= ~3000 keys per server table
 
 
-@pytest.mark.parametrize("world", [2, 4, 8])
-def test_grouped_record_layout_uses_the_unique_buckets(world):
-    """Grouped records (the kBdRecGroup bit beside kBdRecLayout, N > 1): the
-    record placement with the unique layout's ~3072-occurrence source buckets
-    (the servers split them into the unique layout's sub-buckets, each run's
-    records grouped by them after the scatter) — not the 3584 / N records
-    whose bucket count reaches the 16K cap at N = 8."""
-    h = hip()
-    bits = h.bd_record_layout_bit() | h.bd_record_group_bit()
-    P = h.bd_buckets(N_BENCH, world, world | bits)
-    assert P == h.bd_buckets(N_BENCH, world, world)
-    assert P < h.bd_buckets(N_BENCH, world, world | h.bd_record_layout_bit())
-    assert h.bd_offsets(N_BENCH, world, world | bits)[0] == P
-    assert h.bd_scratch_words(N_BENCH, world, world | bits) > P
-    # the servers' split of a grouped layout is the unique one's
-    m = h.srv_sub_buckets(world, N_BENCH, world)
-    assert m > 1 and world * (N_BENCH / P) * 1.25 / m <= 3000
+
+@pytest.mark.gpu
+def test_record_deduper_has_no_server_sub_buckets():
+    """A record-layout deduper routes whole buckets: server sub-buckets
+    (msub = 2) are refused by split_for_servers and, forced past it, by the
+    launcher's host-side check before any launch; with msub = 1 the same call
+    puts every occurrence's key and index at its send-segment position."""
+    import numpy as np
+    import torch
+
+    from swiftsnails_amd.ops.dedup import Deduper
+    from swiftsnails_amd.parallel.router import HashFrag
+
+    dev, nranks, n = torch.device("cuda", 0), 2, 4096
+    hf = HashFrag(nranks, 97)
+    d = Deduper(n, nranks=nranks, frag_map=torch.from_numpy(hf.rank_map().astype(np.int32)),
+                device=dev, record_layout=True)
+    d.lay_n = n
+    d.enable_records()
+    k = np.random.default_rng(5).integers(0, 1500, size=n, dtype=np.int64)
+    keys = torch.from_numpy(k).to(dev)
+    with pytest.raises(RuntimeError, match="split_for_servers: the record layout"):
+        d.split_for_servers(2)
+    d.msub = 2
+    d.usub = torch.zeros(2 * hip().bd_buckets(n, nranks, d.ndest), dtype=torch.int32, device=dev)
+    with pytest.raises(RuntimeError, match="bdedup: the record exchange needs"):
+        d(keys)
+    d.msub, d.usub = 1, None
+    r = d(keys)
+    torch.cuda.synchronize()
+    d.check()
+    # every occurrence j: its key and j at position pos_of[j] of its destination's segment
+    pos = d.pos_of.cpu().numpy().view(np.uint32).astype(np.int64)[:n]
+    assert len(np.unique(pos)) == n
+    np.testing.assert_array_equal(r.ukeys.cpu().numpy()[pos], k)
+    np.testing.assert_array_equal(d.spj.cpu().numpy().view(np.uint32)[pos], np.arange(n))
+    dest = hf.rank_map()[hf.frag_of(k)]
+    np.testing.assert_array_equal(pos // d.ucap, dest)
+    uc = r.ucount.cpu().numpy()
+    np.testing.assert_array_equal(uc, np.bincount(dest, minlength=nranks))
+    assert (pos % d.ucap < uc[dest]).all()
