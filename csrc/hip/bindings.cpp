@@ -541,6 +541,21 @@ PYBIND11_MODULE(_ss_hip, m) {
      py::arg("W"), py::arg("D"), py::arg("neg_per_pair"), py::arg("uvals"), py::arg("ugrad"),
      py::arg("loss"), py::arg("pairs"), py::arg("st"), py::arg("ograd") = 0,
      py::arg("otail") = 0);
+  m.def("w2v_cbow", [](uintptr_t inv_c, uintptr_t inv_w, uintptr_t inv_n, uintptr_t meta, int B,
+                       int W, int D, float neg_per_center, uintptr_t uvals, uintptr_t ugrad,
+                       uintptr_t loss, uintptr_t pairs, uintptr_t st, uintptr_t ograd,
+                       uintptr_t otail) {
+    launch_w2v_cbow(P<const uint32_t>(inv_c), P<const uint32_t>(inv_w), P<const uint32_t>(inv_n),
+                    P<const int32_t>(meta), B, W, D, neg_per_center, P<const float>(uvals),
+                    P<float>(ugrad), P<float>(loss), P<float>(pairs), S(st), P<float>(ograd),
+                    P<float>(otail));
+  }, py::arg("inv_c"), py::arg("inv_w"), py::arg("inv_n"), py::arg("meta"), py::arg("B"),
+     py::arg("W"), py::arg("D"), py::arg("neg_per_center"), py::arg("uvals"), py::arg("ugrad"),
+     py::arg("loss"), py::arg("pairs"), py::arg("st"), py::arg("ograd") = 0,
+     py::arg("otail") = 0);
+  m.def("w2v_cbow_keys", [](uintptr_t keys, long long n, uintptr_t st) {
+    launch_w2v_cbow_keys(P<uint64_t>(keys), n, S(st));
+  }, py::arg("keys"), py::arg("n"), py::arg("stream"));
   m.def("w2v_pp", [](uintptr_t inv_c, uintptr_t inv_w, uintptr_t inv_n, uintptr_t meta, int B,
                      int W, int K, int D, uintptr_t uvals, uintptr_t ograd, uintptr_t gpair,
                      uintptr_t loss, uintptr_t pairs, uintptr_t st, uintptr_t gnc) {

@@ -123,6 +123,14 @@ void launch_w2v_win(const uint32_t* inv_c, const uint32_t* inv_w, const uint32_t
                     const int32_t* meta, int B, int W, int D, float neg_per_pair,
                     const float* uvals, float* ugrad, float* loss_sum, float* pair_sum,
                     hipStream_t st, float* ograd = nullptr, float* otail = nullptr);
+// CBOW on the same batch layout (w2v.hip k_w2v_cbow_bf16): run positions are
+// input rows, centers and negatives output rows; pair_sum counts trained centers
+void launch_w2v_cbow(const uint32_t* inv_c, const uint32_t* inv_w, const uint32_t* inv_n,
+                     const int32_t* meta, int B, int W, int D, float neg_per_center,
+                     const float* uvals, float* ugrad, float* loss_sum, float* pair_sum,
+                     hipStream_t st, float* ograd = nullptr, float* otail = nullptr);
+// flips the namespace bit (1 << 40) of the first n keys of a window-layout batch
+void launch_w2v_cbow_keys(uint64_t* keys, long long n, hipStream_t st);
 void launch_w2v_osort(int P, const uint32_t* bstart, const uint32_t* unum, const uint32_t* ubase,
                       const uint32_t* pj, const uint32_t* luid, uint32_t* ord, uint32_t* items,
                       hipStream_t st, uint8_t* uhot = nullptr);

@@ -674,6 +674,322 @@ __global__ __launch_bounds__(kWG, 4) void k_w2v_win_bf16(
   }
 }
 
+// ---------------------------------------------------------------------------
+// CBOW tile (w2v_arch: cbow): the window layout and shared negatives of the
+// tile above with the roles reversed — the run positions are INPUT rows x_q
+// (syn0), the centers c_t and the negatives n_j OUTPUT rows (syn1neg).  A
+// trained center predicts its word from the mean of its window,
+//     h_t = (1/n_t) Σ_q m_tq x_q,   loss_t = softplus(-h_t·c_t) + (K/S) Σ_j softplus(h_t·n_j)
+// (one positive per center: the negatives' weight is K/S, not n_t·K/S), and
+// the gradients are the true ones of that loss (the mean's 1/n_t reaches gX).
+// With M the 64 x 96 band of m_tq the tile is four GEMMs on the bf16 MFMA
+// (fp32 accumulate) and two diagonal epilogues:
+//     H  = diag(1/n)·(M·X)          64 x D, K = 96 (the band's k-blocks only)
+//     S- = H·Nᵀ                     64 x 64;  s+_t = h_t·c_t
+//     gH = G-·N + diag(g+)·C        64 x D, then scaled 1/n_t
+//     gX = Mᵀ·(gH/n)  96 x D     gN = G-ᵀ·H  64 x D     gC = diag(g+)·H
+// Data flow (its own, not the skip-gram tile's):
+//   * M never exists in memory.  Each lane builds its A fragment — 8 exact
+//     0/1 bf16 — from the meta words in LDS (w2v_pair_ok on mc[t], mw[q]);
+//     1/n_t multiplies the fp32 accumulators, never M.
+//   * 2·D/32 waves own one 32 x 32 tile of H and the same tile of gH, and hold
+//     it in accumulator registers across a barrier, so the result overwrites
+//     an operand that is dead by then: H (bf16) goes over rows 0..63 of X,
+//     gH/n over C.  The fp32 H accumulators stay live until g+ is known and
+//     give gC without a second pass.
+//   * s+ is a lane-group dot (4 lanes per center over the bf16 H and C rows in
+//     LDS, two xor-shuffles) on waves 4..7, which have no S- tile: it runs
+//     beside the four S- tiles of waves 0..3.  The MFMA form would spend two
+//     32 x 32 diagonal blocks to keep 64 of 2048 results and lengthen the
+//     S- waves' chain instead of using the idle ones.
+// LDS: (96 + 64 + 64) rows of D + 8 bf16, G- 64 x 72 bf16, 2464 B of static
+// index / meta / scale arrays:
+//     D = 128: 70144 + 2464 = 72608 B (70.9 KB) -> 2 workgroups per CU (160 KB)
+//     D =  64: 41472 + 2464 = 43936 B (42.9 KB) -> 3
+//     D =  32: 27136 + 2464 = 29600 B (28.9 KB) -> 5 by LDS
+// (the skip-gram tile with its stored G+ takes 83.9 KB at D = 128: one per
+// CU).  These are the workgroups the LDS budget and the launch bound (4 waves
+// per SIMD, <= 128 VGPRs) allow; the occupancy a run reaches has not been
+// read from hardware counters.
+template <int D>
+struct W2vCbowSmem {
+  static constexpr int PB = D + 8;   // bf16 row stride of the X / C / N tiles
+  static constexpr int GB = kS + 8;  // bf16 row stride of G-
+  static constexpr size_t bytes =
+      sizeof(unsigned short) * ((size_t)(kWU + kT + kS) * PB + (size_t)kT * GB);
+};
+
+__device__ __forceinline__ float bf2f(unsigned short b) { return __uint_as_float((uint32_t)b << 16); }
+
+template <int D>
+__global__ __launch_bounds__(kWG, 4) void k_w2v_cbow_bf16(
+    const uint32_t* __restrict__ inv_c, const uint32_t* __restrict__ inv_w,
+    const uint32_t* __restrict__ inv_n, const int32_t* __restrict__ meta, int B, int W,
+    float neg_per_center, const float* __restrict__ uvals, float* __restrict__ ugrad,
+    float* __restrict__ loss_sum, float* __restrict__ pair_sum,
+    float* __restrict__ ograd, float* __restrict__ otail) {
+  using L = W2vCbowSmem<D>;
+  constexpr int PB = L::PB, GB = L::GB, TJ = D / 32;
+  constexpr short kOne = 0x3F80;  // bf16 1.0
+  extern __shared__ __attribute__((aligned(16))) unsigned short smem16[];
+  unsigned short* Xb = smem16;         // [kWU][PB] window rows (syn0): row l = run position t0 + l
+  unsigned short* Cb = Xb + kWU * PB;  // [T][PB]   center rows (syn1neg)
+  unsigned short* Nb = Cb + kT * PB;   // [S][PB]   shared negatives (syn1neg)
+  unsigned short* Gn = Nb + kS * PB;   // [T][GB]   G-
+  unsigned short* Hb = Xb;             // [T][PB]   H, over X once M·X is in registers
+  unsigned short* gHb = Cb;            // [T][PB]   gH/n, over C once s+ and the epilogue read it
+  __shared__ uint32_t rc[kT], rw[kWU], rn[kS];
+  __shared__ int32_t mw[kWU], mc[kT];  // mc: the center's meta, -1 if it does not train
+  __shared__ int uany[kWU];
+  __shared__ float ninv[kT], gp[kT];   // 1/n_t (0: untrained), g+
+  __shared__ float red[kNW];
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int r32 = lane & 31, h = lane >> 5;
+  const long long R = (long long)B + 2 * W;
+  const int ntiles = (B + kT - 1) / kT;
+  const bool own = w < 2 * TJ;  // this wave holds tile (oi, oj) of H and of gH
+  const int oi = w / TJ, oj = w % TJ;
+  float loss = 0.f, ntrained = 0.f;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const long long t0 = (long long)tile * kT;  // first center; its run position is t0 + W
+    if (tid < kWU) {
+      const long long q = t0 + tid;
+      const bool in = tid < kT + 2 * W && q < R;
+      const int32_t m = in ? meta[q] : -1;
+      mw[tid] = m;
+      rw[tid] = m >= 0 ? inv_w[q] : kInv;
+    } else if (tid < kWU + kS) {
+      rn[tid - kWU] = inv_n[(long long)tile * kS + (tid - kWU)];
+    }
+    __syncthreads();
+    if (tid < kT) {  // center t sits at window row t + W
+      const int32_t m = mw[tid + W];
+      int n = 0;
+      if (t0 + tid < B && m >= 0)
+        for (int dq = -W; dq <= W; ++dq) n += w2v_pair_ok(m, mw[tid + W + dq], dq) ? 1 : 0;
+      mc[tid] = n > 0 ? m : -1;
+      rc[tid] = n > 0 ? inv_c[t0 + tid] : kInv;  // an empty window does not train
+      ninv[tid] = n > 0 ? 1.f / (float)n : 0.f;
+      ntrained += n > 0 ? 1.f : 0.f;
+    }
+    __syncthreads();
+    if (tid < kWU) {  // window rows no trained center averaged: no row atomics for them
+      const int32_t mq = mw[tid];
+      int any = 0;
+      if (mq >= 0)
+        for (int t = max(0, tid - 2 * W); t <= min(kT - 1, tid); ++t)
+          any |= w2v_pair_ok(mc[t], mq, tid - (t + W)) ? 1 : 0;
+      uany[tid] = any;
+    }
+    // rows -> bf16 tiles (X, C, N are consecutive rows of stride PB), every
+    // load issued before the first LDS store: one memory round trip per tile
+    {
+      constexpr int NE = (kWU + kT + kS) * (D / 4), PER = (NE + kWG - 1) / kWG;
+      float4 v[PER];
+#pragma unroll
+      for (int i = 0; i < PER; ++i) {
+        const int e = tid + i * kWG, r = e / (D / 4), d = 4 * (e - r * (D / 4));
+        const uint32_t id = e >= NE ? kInv : r < kWU ? rw[r] : r < kWU + kT ? rc[r - kWU] : rn[r - kWU - kT];
+        v[i] = id != kInv ? *reinterpret_cast<const float4*>(uvals + (long long)id * D + d)
+                          : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int i = 0; i < PER; ++i) {
+        const int e = tid + i * kWG, r = e / (D / 4), d = 4 * (e - r * (D / 4));
+        if (e < NE)
+          *reinterpret_cast<uint2*>(smem16 + r * PB + d) =
+              make_uint2(f2bf(v[i].x) | ((uint32_t)f2bf(v[i].y) << 16),
+                         f2bf(v[i].z) | ((uint32_t)f2bf(v[i].w) << 16));
+      }
+    }
+    __syncthreads();
+
+    // ---- H = diag(1/n)·(M·X): only the k-blocks the band of row tile oi reaches
+    f32x16 hacc = {};
+    if (own) {
+      const int t = oi * 32 + r32;
+      const int32_t mt = mc[t];
+      for (int k0 = oi * 32; k0 < oi * 32 + 32 + 2 * W; k0 += 16) {
+        const int kb = k0 + 8 * h;
+        bf16x8 a, b;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          a[j] = w2v_pair_ok(mt, mw[kb + j], kb + j - (t + W)) ? kOne : (short)0;
+          b[j] = (short)Xb[(kb + j) * PB + oj * 32 + r32];
+        }
+        hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, hacc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) hacc[r] *= ninv[oi * 32 + mrow(r, lane)];
+    }
+    __syncthreads();  // every wave is done reading X
+    if (own) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        Hb[(oi * 32 + mrow(r, lane)) * PB + oj * 32 + r32] = f2bf(hacc[r]);
+    }
+    __syncthreads();
+
+    // ---- scores: S- on waves 0..3 (2 x 2 tiles), s+ on waves 4..7
+    if (w < 4) {
+      const int ti = w >> 1, tj = w & 1;
+      f32x16 acc = {};
+#pragma unroll
+      for (int k0 = 0; k0 < D; k0 += 16) {
+        const bf16x8 a = *reinterpret_cast<const bf16x8*>(Hb + (ti * 32 + r32) * PB + k0 + 8 * h);
+        const bf16x8 b = *reinterpret_cast<const bf16x8*>(Nb + (tj * 32 + r32) * PB + k0 + 8 * h);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = ti * 32 + mrow(r, lane), col = tj * 32 + r32;
+        const bool ok = rc[row] != kInv && rn[col] != kInv;
+        Gn[row * GB + col] = f2bf(ok ? neg_per_center * sigm(acc[r]) : 0.f);
+        if (ok) loss += neg_per_center * softplus(acc[r]);
+      }
+    } else {
+      const int t = (w - 4) * 16 + (lane >> 2), p = lane & 3;
+      float s = 0.f;
+#pragma unroll
+      for (int c = 0; c < D / 32; ++c) {
+        const int d = p * (D / 4) + 8 * c;
+        const bf16x8 x = *reinterpret_cast<const bf16x8*>(Hb + t * PB + d);
+        const bf16x8 y = *reinterpret_cast<const bf16x8*>(Cb + t * PB + d);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += bf2f((unsigned short)x[j]) * bf2f((unsigned short)y[j]);
+      }
+      s += __shfl_xor(s, 1, 64);
+      s += __shfl_xor(s, 2, 64);
+      if (p == 0) {
+        const bool ok = rc[t] != kInv;
+        gp[t] = ok ? sigm(s) - 1.f : 0.f;  // d/ds softplus(-s)
+        if (ok) loss += softplus(-s);
+      }
+    }
+    __syncthreads();
+
+    // the tile's gradient rows leave as in the skip-gram tile: occurrence rows
+    // (plain stores; window rows >= 64 of a tile other than the last go to the
+    // tail buffer: they are rows 0.. of the next tile) or row atomics.
+    // kind 0: centers, 1: window rows, 2: negatives
+    auto emit = [&](int kind, int ti, int tj, const f32x16& acc) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = ti * 32 + mrow(r, lane), col = tj * 32 + r32;
+        if (ograd) {
+          long long orow = -1;
+          if (kind == 0) {
+            if (t0 + row < B) orow = t0 + row;
+          } else if (kind == 1) {
+            const long long q = t0 + row;
+            if (row < kT + 2 * W && q < R) {
+              if (row < kT || tile == ntiles - 1)
+                orow = B + q;
+              else
+                otail[((long long)tile * 2 * W + (row - kT)) * D + col] = acc[r];
+            }
+          } else {
+            orow = B + R + (long long)tile * kS + row;
+          }
+          if (orow >= 0) ograd[orow * D + col] = acc[r];
+          continue;
+        }
+        const uint32_t dst = kind == 0 ? rc[row] : (kind == 1 ? (uany[row] ? rw[row] : kInv) : rn[row]);
+        if (dst == kInv) continue;
+        atomicAdd(ugrad + (long long)dst * D + col, acc[r]);
+      }
+    };
+
+    // ---- gH = (G-·N + diag(g+)·C)/n in registers; gC = diag(g+)·H from the fp32 H
+    f32x16 gacc = {};
+    if (own) {
+#pragma unroll
+      for (int k0 = 0; k0 < kS; k0 += 16) {
+        const int kb = k0 + 8 * h;
+        const bf16x8 a = *reinterpret_cast<const bf16x8*>(Gn + (oi * 32 + r32) * GB + kb);
+        bf16x8 b;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) b[j] = (short)Nb[(kb + j) * PB + oj * 32 + r32];
+        gacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, gacc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = oi * 32 + mrow(r, lane), col = oj * 32 + r32;
+        const float g = gp[row];
+        gacc[r] = (gacc[r] + g * bf2f(Cb[row * PB + col])) * ninv[row];
+        hacc[r] *= g;
+      }
+      emit(0, oi, oj, hacc);
+    }
+    __syncthreads();  // every wave is done reading C (and N)
+    if (own) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        gHb[(oi * 32 + mrow(r, lane)) * PB + oj * 32 + r32] = f2bf(gacc[r]);
+    }
+    __syncthreads();
+
+    // ---- gX = Mᵀ·(gH/n) (3 x TJ tiles, the band's centers only), gN = G-ᵀ·H (2 x TJ)
+    for (int tt = w; tt < 5 * TJ; tt += kNW) {
+      const bool wx = tt < 3 * TJ;
+      const int q = wx ? tt : tt - 3 * TJ;
+      const int ti = q / TJ, tj = q % TJ;
+      f32x16 acc = {};
+      if (wx) {
+        const int l = ti * 32 + r32;
+        const int32_t ml = mw[l];
+        for (int k0 = max(0, ti * 32 - 2 * W) & ~15; k0 < min(kT, ti * 32 + 32); k0 += 16) {
+          const int kb = k0 + 8 * h;
+          bf16x8 a, b;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            a[j] = w2v_pair_ok(mc[kb + j], ml, l - (kb + j + W)) ? kOne : (short)0;
+            b[j] = (short)gHb[(kb + j) * PB + tj * 32 + r32];
+          }
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+        }
+      } else {
+#pragma unroll
+        for (int k0 = 0; k0 < kT; k0 += 16) {
+          const int kb = k0 + 8 * h;
+          bf16x8 a, b;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            a[j] = (short)Gn[(kb + j) * GB + ti * 32 + r32];
+            b[j] = (short)Hb[(kb + j) * PB + tj * 32 + r32];
+          }
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+        }
+      }
+      emit(wx ? 1 : 2, ti, tj, acc);
+    }
+    __syncthreads();  // the next tile overwrites the LDS tiles
+  }
+  for (int o = 32; o > 0; o >>= 1) loss += __shfl_down(loss, o, 64);
+  if (lane == 0) red[w] = loss;
+  __syncthreads();
+  if (tid == 0 && loss_sum) {
+    float tot = 0.f;
+#pragma unroll
+    for (int i = 0; i < kNW; ++i) tot += red[i];
+    ctr_addf(loss_sum, tot);
+  }
+  if (w == 0 && pair_sum) {  // the centers' flags live in wave 0 (tid < kT)
+    for (int o = 32; o > 0; o >>= 1) ntrained += __shfl_down(ntrained, o, 64);
+    if (lane == 0) ctr_addf(pair_sum, ntrained);  // trained centers
+  }
+}
+
+// CBOW reverses the namespaces of a window-layout batch: the run positions
+// are input rows (plain ids), the centers output rows (id | 1 << 40, where
+// the negatives already live).  Flipping bit 40 of the first B + R keys after
+// any batcher wrote them leaves the batchers as they are.
+__global__ __launch_bounds__(256) void k_w2v_cbow_keys(uint64_t* __restrict__ keys, long long n) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) keys[i] ^= 1ull << 40;
+}
+
 // ---- atomic-free gradient merge of the windowed tile (SS_W2V_GRAD=reduce)
 //
 // Measured: the tile's row atomics (~52K rows of 512 B per 16K-center step,
@@ -1703,6 +2019,39 @@ void launch_w2v_win(const uint32_t* inv_c, const uint32_t* inv_w, const uint32_t
       throw_error("w2v_win: D must be 32, 64 or 128");
   }
   check_launch("k_w2v_win_bf16");
+}
+
+void launch_w2v_cbow(const uint32_t* inv_c, const uint32_t* inv_w, const uint32_t* inv_n,
+                     const int32_t* meta, int B, int W, int D, float neg_per_center,
+                     const float* uvals, float* ugrad, float* loss_sum, float* pair_sum,
+                     hipStream_t st, float* ograd, float* otail) {
+  if (B <= 0) return;
+  if (W < 1 || W > kW2vMaxWindow) throw_error("w2v_cbow: window must be in [1, 15]");
+  if (ograd && !otail && B > kT) throw_error("w2v_cbow: occurrence rows need the tail buffer");
+  const int tiles = (B + kT - 1) / kT;
+  const int grid = w2v_tile_grid(tiles, ograd == nullptr);
+  switch (D) {
+#define SS_W2VC_CASE(DD)                                                                     \
+  case DD:                                                                                   \
+    smem_attr_once<k_w2v_cbow_bf16<DD>>(W2vCbowSmem<DD>::bytes);                             \
+    hipLaunchKernelGGL(k_w2v_cbow_bf16<DD>, dim3(grid), dim3(kWG), W2vCbowSmem<DD>::bytes, st,  \
+                       inv_c, inv_w, inv_n, meta, B, W, neg_per_center, uvals, ugrad,         \
+                       loss_sum, pair_sum, ograd, otail);                                      \
+    break;
+    SS_W2VC_CASE(32)
+    SS_W2VC_CASE(64)
+    SS_W2VC_CASE(128)
+#undef SS_W2VC_CASE
+    default:
+      throw_error("w2v_cbow: D must be 32, 64 or 128");
+  }
+  check_launch("k_w2v_cbow_bf16");
+}
+
+void launch_w2v_cbow_keys(uint64_t* keys, long long n, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_w2v_cbow_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, keys, n);
+  check_launch("k_w2v_cbow_keys");
 }
 
 // SS_W2V_PP_STAGES: pipeline stages of the K <= 5 kernel, 3 (default) or 4;

@@ -356,7 +356,8 @@ def build_worker(cfg: Config):
                             negatives=int(cfg.get("negatives", 5)),
                             mode=cfg.get("w2v_mode", "window"),
                             sentence_len=int(cfg.get("sentence_len", 24)),
-                            neg_mode=cfg.get("neg_mode", "shared"))
+                            neg_mode=cfg.get("neg_mode", "shared"),
+                            arch=cfg.get("w2v_arch", "skipgram"))
         dim = int(cfg.get("dim", 128))
         opt, init = make_w2v_table_args(dim, opt)
         cap = int(cfg.get("table_capacity", 0) or 2 * data.vocab / nserv / load + 1024)
@@ -461,7 +462,7 @@ def run_training(cfg: Config, steps: Optional[int] = None, warmup: int = 0,
         stats["w2v"] = {"layout": d.mode, "neg_mode": getattr(d, "neg_mode", "shared"),
                         "mfma": ("none (fp32 dot products)" if w.per_pair else
                                  "bf16" if d.mode == "window" or w.mfma_bf16 else "fp32"),
-                        "negatives": d.negatives}
+                        "negatives": d.negatives, "arch": getattr(d, "arch", "skipgram")}
     if ctx.evict_period > 0:
         stats["evict"] = {"period": ctx.evict_period, "evicted": ctx.evicted}
     m = ctx.engine.metrics.counters

@@ -46,9 +46,16 @@ class W2VLayout:
     ``neg_mode="shared"`` (default): each 64-center tile trains against 64
     shared negatives weighted to K per pair (GEMMs on the MFMA);
     ``"per_pair"`` (window mode): word2vec's own objective, K negatives drawn
-    for every positive pair (B x 2W x K negative keys per step)."""
+    for every positive pair (B x 2W x K negative keys per step).
+
+    ``arch="skipgram"`` (default) or ``"cbow"`` (window mode, shared
+    negatives): a center's word is predicted from the mean of its window's
+    input vectors, one positive per center with K negatives spread over the
+    tile's 64 shared ones.  Same batch layout with the namespaces reversed:
+    run positions are input rows, centers output rows (``id | 1<<40``)."""
 
     neg_mode = "shared"
+    arch = "skipgram"
 
     @property
     def n_neg(self) -> int:
@@ -94,6 +101,10 @@ class W2VLayout:
             raise ValueError(f"word2vec neg_mode must be shared or per_pair, not {self.neg_mode!r}")
         if self.neg_mode == "per_pair" and (self.mode != "window" or not 1 <= self.negatives <= 16):
             raise ValueError("per_pair negatives: window mode, 1..16 negatives per pair")
+        if self.arch not in ("skipgram", "cbow"):
+            raise ValueError(f"word2vec arch must be skipgram or cbow, not {self.arch!r}")
+        if self.arch == "cbow" and (self.mode != "window" or self.neg_mode != "shared"):
+            raise ValueError("cbow: window mode with shared negatives only")
 
 
 @dataclass
@@ -107,6 +118,7 @@ class W2VSynth(W2VLayout):
     mode: str = "window"           # window | pairs (see W2VLayout)
     sentence_len: int = 24         # window mode: tokens per synthetic sentence
     neg_mode: str = "shared"       # shared | per_pair (see W2VLayout)
+    arch: str = "skipgram"         # skipgram | cbow (see W2VLayout)
 
     def __post_init__(self):
         self._check_mode()
@@ -138,7 +150,8 @@ def make_w2v_table_args(dim: int, optimizer: Optional[Optimizer] = None):
 
 
 class Word2VecWorker(PipelinedWorker):
-    """Trains skip-gram embeddings through a ``PSEngine`` (dim = embedding size)."""
+    """Trains skip-gram or CBOW (``data.arch``) embeddings through a
+    ``PSEngine`` (dim = embedding size)."""
 
     def __init__(self, engine, data: W2VSynth, rank: int = 0, world: int = 1,
                  active: bool = True):
@@ -177,6 +190,7 @@ class Word2VecWorker(PipelinedWorker):
         self.occ_reduce = (self.window_mode and engine.gpu and
                            all(getattr(d, "mode", None) == "bucket" for d in engine.dedupers))
         self.per_pair = getattr(data, "neg_mode", "shared") == "per_pair"
+        self.cbow = getattr(data, "arch", "skipgram") == "cbow"
         if self.per_pair and not self.occ_reduce:
             raise ValueError("per_pair negatives need the bucketed dedup (SS_DEDUP=bucket)")
         if self.occ_reduce:
@@ -236,6 +250,14 @@ class Word2VecWorker(PipelinedWorker):
         if self.window_mode:
             kw["meta"] = self.meta[slot]
         self.data.generate(step, self.rank, self.world, self.keys[slot], stream=stream, **kw)
+        if self.cbow:
+            # centers to the output namespace, run positions to the input one,
+            # behind the batch on the stream the source wrote it on (None: the
+            # current stream, where every source puts its work then)
+            st = stream if stream is not None else torch.cuda.current_stream()
+            st = st.cuda_stream if hasattr(st, "cuda_stream") else int(st)
+            hip().w2v_cbow_keys(self.keys[slot].data_ptr(),
+                                self.data.batch_size + self.data.run_len, st)
         return self.keys[slot]
 
     def _fused(self, rnd):
@@ -279,10 +301,11 @@ class Word2VecWorker(PipelinedWorker):
             return
         if self.window_mode:
             occ = self.occ_reduce
-            h.w2v_win(ptr, ptr + B * es, ptr + (B + d.run_len) * es, self.meta[slot].data_ptr(),
-                      B, d.window, self.engine.dim, d.neg_per_pair, rnd.uvals.data_ptr(),
-                      rnd.ugrad.data_ptr(), self._acc[0].data_ptr(), self._acc[1].data_ptr(),
-                      st, self.ograd.data_ptr() if occ else 0, self.otail.data_ptr() if occ else 0)
+            tile = h.w2v_cbow if self.cbow else h.w2v_win
+            tile(ptr, ptr + B * es, ptr + (B + d.run_len) * es, self.meta[slot].data_ptr(),
+                 B, d.window, self.engine.dim, d.neg_per_pair, rnd.uvals.data_ptr(),
+                 rnd.ugrad.data_ptr(), self._acc[0].data_ptr(), self._acc[1].data_ptr(),
+                 st, self.ograd.data_ptr() if occ else 0, self.otail.data_ptr() if occ else 0)
             if occ:
                 fa = self._fused(rnd)
                 h.w2v_oreduce(self.items[slot].data_ptr(), d.n_keys, self.ord[slot].data_ptr(),
@@ -304,7 +327,9 @@ class Word2VecWorker(PipelinedWorker):
 
     def step_pairs(self) -> float:
         """Positive pairs trained in the last step (window layout: counted by
-        the tile kernel; pairs layout: B x 2W).  Syncs."""
+        the tile kernel; pairs layout: B x 2W).  CBOW has one positive per
+        trained center (a center with a non-empty window): the count is of
+        those.  Syncs."""
         if not self.active:
             return 0.0
         if self.window_mode:
@@ -312,7 +337,8 @@ class Word2VecWorker(PipelinedWorker):
         return float(self.data.batch_size * self.data.contexts)
 
     def mean_loss(self) -> float:
-        """Mean SGNS loss per positive pair (incl. its negatives) of the last step."""
+        """Mean SGNS loss per positive pair (incl. its negatives) of the last
+        step; CBOW: per trained center."""
         if not self.window_mode:
             return super().mean_loss()
         n = self.step_pairs()
@@ -345,6 +371,31 @@ def sgns_window_reference(V: np.ndarray, U: np.ndarray, N: np.ndarray, mask: np.
     Gn = cw * sig(Sn)
     loss = np.where(mask, sp(-Sp), 0.0).sum() + (cw * sp(Sn)).sum()
     return loss, n.sum(), Gp @ U + Gn @ N, Gp.T @ V, Gn.T @ V
+
+
+def cbow_window_reference(X: np.ndarray, C: np.ndarray, N: np.ndarray, mask: np.ndarray,
+                          neg_per_center: float):
+    """fp64 reference of one CBOW window tile.  X [Q,D] window rows (input
+    vectors), C [T,D] center rows and N [S,D] shared negatives (output
+    vectors), mask [T,Q] the same band as skip-gram's.  A center with n_t > 0
+    window rows trains: h_t is their mean, its loss softplus(-h_t.c_t) +
+    neg_per_center * sum_j softplus(h_t.n_j).  Returns (loss, trained, gX, gC,
+    gN), the gradients of that loss."""
+    X, C, N = (a.astype(np.float64) for a in (X, C, N))
+    sig = lambda z: 1.0 / (1.0 + np.exp(-z))  # noqa: E731
+    sp = lambda z: np.maximum(z, 0) + np.log1p(np.exp(-np.abs(z)))  # noqa: E731
+    n = mask.sum(1).astype(np.float64)
+    on = n > 0
+    A = mask / np.where(on, n, 1.0)[:, None]  # diag(1/n) M, zero rows where untrained
+    H = A @ X
+    s_p = (H * C).sum(1)
+    S_n = H @ N.T
+    gp = np.where(on, sig(s_p) - 1.0, 0.0)
+    Gn = np.where(on[:, None], neg_per_center * sig(S_n), 0.0)
+    loss = np.where(on, sp(-s_p), 0.0).sum() + \
+        neg_per_center * np.where(on[:, None], sp(S_n), 0.0).sum()
+    gH = gp[:, None] * C + Gn @ N
+    return loss, int(on.sum()), A.T @ gH, gp[:, None] * H, Gn.T @ H
 
 
 def sgns_pp_reference(V: np.ndarray, U: np.ndarray, N: np.ndarray, mask: np.ndarray):

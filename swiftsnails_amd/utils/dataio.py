@@ -243,13 +243,14 @@ class FileCorpusSource(W2VLayout):
                  rank: int = 0, world: int = 1, min_count: int = 1, sample: float = 0.0,
                  seed: int = 1234, nthreads: int = 8, prefetch: int = 3,
                  pin: Optional[bool] = None, resident: Optional[str] = None, device=None,
-                 mode: str = "window", neg_mode: str = "shared"):
+                 mode: str = "window", neg_mode: str = "shared", arch: str = "skipgram"):
         self.corpus = host().Corpus(path, nthreads, rank, world, min_count, sample)
         self.batch_size = int(batch_size)
         self.window = int(window)
         self.negatives = int(negatives)
         self.mode = mode
         self.neg_mode = neg_mode
+        self.arch = arch
         self._check_mode()
         self.seed = int(seed) + 7919 * rank
         self.nthreads = nthreads
@@ -386,7 +387,8 @@ def make_ctr_source(cfg, rank: int = 0, world: int = 1, device=None):
 
 def make_corpus_source(cfg, rank: int = 0, world: int = 1, device=None):
     """Config keys: data_path, batch_size, window, negatives, min_count, sample,
-    data_resident (auto|hbm|host), w2v_mode (window|pairs), neg_mode (shared|per_pair)."""
+    data_resident (auto|hbm|host), w2v_mode (window|pairs), neg_mode (shared|per_pair),
+    w2v_arch (skipgram|cbow)."""
     path, shard, nshards = rank_data_path(cfg.get("data_path"), rank, world)
     return FileCorpusSource(path, batch_size=int(cfg.get("batch_size", 16384)),
                             seed=1234 + 7919 * (rank - shard),  # negatives differ per rank
@@ -397,4 +399,5 @@ def make_corpus_source(cfg, rank: int = 0, world: int = 1, device=None):
                             nthreads=int(cfg.get("data_threads", 8)),
                             resident=cfg.get("data_resident", "auto"), device=device,
                             mode=cfg.get("w2v_mode", "window"),
-                            neg_mode=cfg.get("neg_mode", "shared"))
+                            neg_mode=cfg.get("neg_mode", "shared"),
+                            arch=cfg.get("w2v_arch", "skipgram"))
