@@ -520,6 +520,12 @@ PYBIND11_MODULE(_ss_hip, m) {
                       P<const float>(uvals), P<float>(ugrad), P<float>(loss), P<float>(pred),
                       S(st));
   });
+  m.def("ffm_fwd_bwd", [](uintptr_t inv, uintptr_t labels, int B, int F, int K, uintptr_t uvals,
+                          uintptr_t ugrad, uintptr_t loss, uintptr_t pred, uintptr_t st) {
+    launch_ffm_fwd_bwd(P<const uint32_t>(inv), P<const float>(labels), B, F, K,
+                       P<const float>(uvals), P<float>(ugrad), P<float>(loss), P<float>(pred),
+                       S(st));
+  });
   m.def("w2v_sgns", [](uintptr_t inv_c, uintptr_t inv_x, uintptr_t inv_n, int B, int C, int D,
                        float neg_scale, uintptr_t uvals, uintptr_t ugrad, uintptr_t loss,
                        uintptr_t st, int bf16) {

@@ -167,6 +167,11 @@ void launch_fm_fwd_bwd(const uint32_t* inv, const float* labels, int B, int F, i
                        const float* uvals, float* ugrad, float* loss_sum, float* pred,
                        hipStream_t st);
 
+// --- ffm.hip (field-aware FM: rows [w | v_0..v_{F-1}], dim = 1 + F*K)
+void launch_ffm_fwd_bwd(const uint32_t* inv, const float* labels, int B, int F, int K,
+                        const float* uvals, float* ugrad, float* loss_sum, float* pred,
+                        hipStream_t st);
+
 // --- segreduce.hip
 int sr_nbins(long long max_unique);
 int sr_nchunks(long long n);

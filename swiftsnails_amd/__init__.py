@@ -16,7 +16,7 @@ Public API (mirrors the reference umbrella header /root/reference/src/swiftsnail
 * routing      : ``HashFrag`` (key -> fragment -> server)
 * config       : ``Config``, ``global_config`` (``key: value`` files)
 * checkpoints  : ``swiftsnails_amd.utils.checkpoint``
-* models       : sparse LR, word2vec (SGNS), FM, dense LR
+* models       : sparse LR, word2vec (SGNS), FM, field-aware FM, dense LR
 """
 from __future__ import annotations
 
@@ -44,6 +44,7 @@ def __getattr__(name):  # lazy: GPU modules import torch/HIP on first use
         "SparseLRWorker": ("models.sparse_lr", "SparseLRWorker"),
         "Word2VecWorker": ("models.word2vec", "Word2VecWorker"),
         "FMWorker": ("models.fm", "FMWorker"),
+        "FFMWorker": ("models.ffm", "FFMWorker"),
         "DenseLR": ("models.dense_lr", "DenseLR"),
         "GlobalParamCache": ("access", "GlobalParamCache"),
         "global_pull_access": ("access", "global_pull_access"),
@@ -61,5 +62,5 @@ def __getattr__(name):  # lazy: GPU modules import torch/HIP on first use
 __all__ = ["Config", "global_config", "HashFrag", "InitConfig", "Optimizer", "EvictRule",
            "HbmTable", "HostTable", "PSEngine", "SwiftMaster", "SwiftServer", "SwiftWorker",
            "BaseAlgorithm", "PSContext", "run_training", "SparseLRWorker", "Word2VecWorker",
-           "FMWorker", "DenseLR", "GlobalParamCache", "global_pull_access", "global_push_access",
+           "FMWorker", "FFMWorker", "DenseLR", "GlobalParamCache", "global_pull_access", "global_push_access",
            "set_global_target"]

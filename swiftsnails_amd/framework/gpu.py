@@ -299,6 +299,7 @@ class PSContext:
 
 def build_worker(cfg: Config):
     """(ctx, worker) for the configured model."""
+    from ..models.ffm import FFMWorker, check_ffm_shape, ffm_table_args
     from ..models.fm import FMWorker, fm_table_args
     from ..models.sparse_lr import CtrSynth, SparseLRWorker
     from ..models.word2vec import W2VSynth, Word2VecWorker, make_w2v_table_args
@@ -323,7 +324,7 @@ def build_worker(cfg: Config):
         dev = torch.device("cuda", int(os.environ.get("SS_DEVICE",
                                                       os.environ.get("LOCAL_RANK", "0"))))
         torch.cuda.set_device(dev)
-    if model in ("sparse_lr", "fm"):
+    if model in ("sparse_lr", "fm", "ffm"):
         if cfg.get("data_path", ""):
             from ..utils.dataio import make_ctr_source
             data = make_ctr_source(cfg, rank, world, device=dev)
@@ -332,8 +333,18 @@ def build_worker(cfg: Config):
                             num_fields=int(cfg.get("num_fields", 39)),
                             num_features=int(float(cfg.get("num_features", 1e9))),
                             tail_frac=float(cfg.get("tail_frac", 0.1)))
-        dim = 1 if model == "sparse_lr" else int(cfg.get("dim", 9))
-        init = InitConfig("zero") if model == "sparse_lr" else fm_table_args(dim - 1, opt)[1]
+        if model == "ffm":
+            # rows [w | v_0..v_{F-1}]: the width follows from the fields and ffm_k
+            ffm_k = int(cfg.get("ffm_k", 4))
+            dim = check_ffm_shape(data.num_fields, ffm_k)
+            if int(cfg.get("dim", dim)) != dim:
+                raise ValueError(f"model ffm: dim is 1 + num_fields * ffm_k = {dim} "
+                                 f"({data.num_fields} fields, ffm_k {ffm_k}); the config says "
+                                 f"{cfg.get('dim')}")
+            init = ffm_table_args(ffm_k, opt)[1]
+        else:
+            dim = 1 if model == "sparse_lr" else int(cfg.get("dim", 9))
+            init = InitConfig("zero") if model == "sparse_lr" else fm_table_args(dim - 1, opt)[1]
         cap = int(cfg.get("table_capacity", 0) or data.num_features / nserv / load + 1024)
         # sparse LR may ship every occurrence at N>1 (exchange: records /
         # SS_XCHG=records; PSEngine), else each source's unique keys
@@ -343,8 +354,12 @@ def build_worker(cfg: Config):
         xch = "unique" if xch == "auto" else xch
         ctx = PSContext(cfg, dim, opt, init, data.batch_size * data.num_fields, cap,
                         exchange=xch if model == "sparse_lr" else "unique")
-        cls = SparseLRWorker if model == "sparse_lr" else FMWorker
-        w = cls(ctx.engine, data, rank=ctx.rank, world=world, active=ctx.is_worker)
+        if model == "ffm":
+            w = FFMWorker(ctx.engine, data, ffm_k, rank=ctx.rank, world=world,
+                          active=ctx.is_worker)
+        else:
+            cls = SparseLRWorker if model == "sparse_lr" else FMWorker
+            w = cls(ctx.engine, data, rank=ctx.rank, world=world, active=ctx.is_worker)
     elif model == "word2vec":
         if cfg.get("data_path", ""):
             from ..utils.dataio import make_corpus_source
