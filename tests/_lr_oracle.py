@@ -132,7 +132,7 @@ class Dataset:
         bytes, each cut moved forward to the next line start."""
         starts = np.concatenate([[0], np.cumsum([len(b) for b in self.lines])])
         size = int(starts[-1])
-        cut = [int(np.searchsorted(starts, size * i // world)) for i in range(world)] + [ROWS]
+        cut = [int(np.searchsorted(starts, size * i // world)) for i in range(world)] + [len(self.lines)]
         return cut[rank], cut[rank + 1]
 
     def batch(self, step: int, batch: int = B, rank: int = 0, world: int = 1):

@@ -19,11 +19,20 @@ Measured on an MI355X, largest |kernel - fp64| / tol (printed as ``MARGIN``;
 reported, not tuned).  Kernel cases in parameter order: pred 0.001 0.002 0.002
 0.002 0.004 0.003, loss <= 0.001, gradient 0.000 0.001 0.001 0.001 0.002 0.003;
 EMPTY / duplicates: gradient 0.006 / 0.008; worker: SGD 0.001, AdaGrad 0.056.
+
+Beside those figures every kernel case is held to ``_ffm_oracle.key_gradient``'s
+derived bounds (``dz`` for the sum the kernel forms, ``eG``, ``pred`` and the
+summed loss with the counter's shards; SAFETY = 2), printed as ``MARGIN derived``:
+the six shapes pred 0.011-0.090, loss <= 0.017, gradient 0.017-0.111; EMPTY /
+duplicates 0.019 / 0.032; all 157 legal shapes (``test_kernel_every_legal_shape``)
+pred 0.174, loss 0.014, gradient 0.100; a hot id with 2112 occurrences
+(``test_kernel_hot_id``) gradient 0.021-0.146, its own row <= 0.001.
 """
 import numpy as np
 import pytest
 import torch
 
+import _ffm_oracle as FO
 from _lr_oracle import U32, U_G
 
 pytestmark = pytest.mark.gpu
@@ -38,8 +47,9 @@ def dev():
     return torch.device("cuda", 0)
 
 
-def _run_kernel(dev, inv, rows, y, F, K):
-    """(pred, loss, ugrad) of one launch on ``inv`` [B, F] uint32, ``rows`` [U, dim]."""
+def _run_kernel(dev, inv, rows, y, F, K, with_pred=True):
+    """(pred, loss, ugrad) of one launch on ``inv`` [B, F] uint32, ``rows`` [U, dim];
+    ``with_pred=False``: the worker's form, no ``pred`` buffer."""
     from swiftsnails_amd._native import hip
 
     B = len(y)
@@ -48,9 +58,31 @@ def _run_kernel(dev, inv, rows, y, F, K):
     g, loss = torch.zeros_like(tr), torch.zeros(256 * 32, device=dev)
     pred = torch.empty(B, device=dev)
     hip().ffm_fwd_bwd(ti.data_ptr(), ty.data_ptr(), B, F, K, tr.data_ptr(), g.data_ptr(),
-                      loss.data_ptr(), pred.data_ptr(), torch.cuda.current_stream().cuda_stream)
+                      loss.data_ptr(), pred.data_ptr() if with_pred else 0,
+                      torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
-    return pred.cpu().numpy(), loss.sum().item(), g.cpu().numpy()
+    return (pred.cpu().numpy() if with_pred else None), loss.sum().item(), g.cpu().numpy()
+
+
+def _ratio(d, tol):
+    """|difference| / bound; 0 where both are 0, inf where only the bound is."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(d == 0, 0.0, np.abs(d) / tol)
+
+
+def _derived(out, r):
+    """(pred, loss, gradient) margins of a launch against ``_ffm_oracle.key_gradient``'s
+    fp64 values and derived bounds (its module docstring; SAFETY = 2)."""
+    pred, loss, g = out
+    rp = float(_ratio(pred - r.p, r.tol_p).max()) if pred is not None else 0.0
+    rl = float(abs(loss - r.loss.sum()) / r.tol_loss)
+    return rp, rl, float(_ratio(g - r.G, FO.SAFETY * r.eG).max())
+
+
+def _check_derived(label, out, r):
+    rp, rl, rg = _derived(out, r)
+    print(f"MARGIN derived {label}: pred {rp:.3f} loss {rl:.3f} grad {rg:.3f}")
+    assert rp <= 1 and rl <= 1 and rg <= 1, (label, rp, rl, rg)
 
 
 def _check_kernel(label, out, ref, F, K):
@@ -74,6 +106,8 @@ def test_kernel_matches_reference(dev, F, K, B):
     out = _run_kernel(dev, np.arange(B * F).reshape(B, F), rows, y, F, K)
     l, p, G = ffm_reference(rows.reshape(B, F, dim), y)
     _check_kernel(f"kernel F {F} K {K}", out, (l, p, G.reshape(B * F, dim)), F, K)
+    _check_derived(f"kernel F {F} K {K}", out,
+                   FO.key_gradient(np.arange(B * F).reshape(B, F), rows, y, K))
     g = out[2].reshape(B, F, dim)
     for i in range(F):  # the (i, i) block is never written
         assert not g[:, i, 1 + i * K:1 + (i + 1) * K].any()
@@ -101,7 +135,89 @@ def test_kernel_empty_and_duplicates(dev, F, K):
     want = np.zeros((U + 5, dim))
     np.add.at(want, inv[valid], G[valid])
     _check_kernel(f"empty/dup F {F} K {K}", out, (l, p, want), F, K)
+    _check_derived(f"empty/dup F {F} K {K}", out, FO.key_gradient(inv, rows, y, K))
     assert p[0] == 0.5 and not out[2][np.setdiff1d(np.arange(U + 5), inv[valid])].any()
+
+
+LEGAL = [(F, K) for K in (2, 4, 8) for F in range(2, 65) if F * K <= 256]
+
+
+def _planted_batch(rng, F, K, B, dup_rows=1):
+    """A small batch for one shape: ids shared between samples (about B F / 4
+    values, three more rows unused), about 15 % EMPTY, sample 0 all EMPTY, sample 1
+    with one id at two columns; rows of scale (F (F - 1) K / 2)^-1/4."""
+    dim = 1 + F * K
+    U = max(2, B * F // 4)
+    rows = ((F * (F - 1) * K / 2) ** -0.25 * rng.standard_normal((U + 3, dim))).astype(np.float32)
+    inv = rng.integers(0, U, (B, F))
+    inv[rng.random((B, F)) < 0.15] = INVALID
+    inv[0] = INVALID
+    inv[1, [0, F - 1]] = 1
+    y = (rng.random(B) < 0.4).astype(np.float32)
+    return inv, rows, y, U
+
+
+def test_kernel_every_legal_shape(dev):
+    """All 157 legal (F, K), every one within the derived bound; the table of
+    (G, di) the sweep covers is asserted, so it cannot silently shrink."""
+    assert len(LEGAL) == 157
+    table, worst = {}, np.zeros(3)
+    for F, K in LEGAL:
+        dim, G, di = FO.geometry(F, K)
+        table[(F, K)] = (G, di)
+        B = 2 * (256 // G) + 1
+        inv, rows, y, U = _planted_batch(np.random.default_rng(1000 * K + F), F, K, B)
+        out = _run_kernel(dev, inv, rows, y, F, K)
+        r = FO.key_gradient(inv, rows, y, K)
+        m = _derived(out, r)
+        worst = np.maximum(worst, m)
+        assert max(m) <= 1, (F, K, m)
+        g = out[2]
+        used = np.unique(inv[inv != INVALID])
+        assert not g[np.setdiff1d(np.arange(U + 3), used)].any()   # unused ids: exactly 0
+        live = inv != INVALID
+        for i in range(F):                                         # diagonal blocks: exactly 0
+            only = np.setdiff1d(inv[:, i][live[:, i]], inv[:, np.arange(F) != i][live[:, np.arange(F) != i]])
+            assert not g[only, 1 + i * K:1 + (i + 1) * K].any(), (F, K, i)
+        assert r.p[0] == 0.5 and out[0][0] == 0.5
+    print(f"MARGIN derived every legal shape: pred {worst[0]:.3f} loss {worst[1]:.3f} "
+          f"grad {worst[2]:.3f}")
+    by_g = {G: {di for g2, di in table.values() if g2 == G} for G in (16, 64, 256)}
+    assert by_g == {16: {0, 1, 2, 3}, 64: {0, 1, 2, 3}, 256: set(range(8))}, by_g
+    # both sides of both regime edges of ``ffm_group``, for every K
+    for lo, hi in (((7, 2), (8, 2)), ((5, 4), (6, 4)), ((3, 8), (4, 8))):
+        assert table[lo][0] == 16 and table[hi][0] == 64
+        assert lo[0] * (1 + lo[0] * lo[1]) <= 128 < hi[0] * (1 + hi[0] * hi[1])
+    for K in (2, 4, 8):
+        assert table[(16, K)][0] == 64 and table[(17, K)][0] == 256
+    assert table[(3, 8)] == (16, 0) and table[(17, 2)] == (256, 7)
+    assert len({(K - 1 - F * K) % 32 for F, K in LEGAL}) == 16  # every padding of ``ffm_row_stride``
+
+
+@pytest.mark.parametrize("F,K", [(5, 2), (13, 4), (39, 4)])
+def test_kernel_hot_id(dev, F, K):
+    """One id at the same column of all 2048 samples and at a second column of
+    64 of them: 2112 atomics into every float of one gradient row, from two
+    partner blocks, within ``n u sum |g b|`` and the rest of the derived bound
+    (a worst case over every order of 2112 atomics: measured, the hot row uses
+    about a thousandth of it, so this holds a gross error of that row, such as a
+    lost occurrence, and not its rounding); also without ``pred``, the worker's
+    form."""
+    B = 2048
+    rng = np.random.default_rng(F)
+    inv, rows, y, U = _planted_batch(rng, F, K, B)
+    c1, c2 = 1, 3
+    inv[inv == 0] = 2                      # id 0 is the hot one, at its two columns only
+    inv[:, c1] = 0
+    inv[rng.choice(B, 64, replace=False), c2] = 0
+    r = FO.key_gradient(inv, rows, y, K)
+    assert r.cnt[0] == B + 64
+    for with_pred in (True, False):
+        out = _run_kernel(dev, inv, rows, y, F, K, with_pred)
+        _check_derived(f"hot id F {F} K {K} pred {int(with_pred)}", out, r)
+        hot = float(_ratio(out[2][0] - r.G[0], FO.SAFETY * r.eG[0]).max())
+        print(f"MARGIN derived hot row F {F} K {K}: grad {hot:.3f}")
+        assert hot <= 1
 
 
 def _export(table):
