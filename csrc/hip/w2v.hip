@@ -25,33 +25,14 @@
 #include "ss_launch.h"
 #include "scan.h"
 #include "ss/w2v_window.h"
+#include "w2v_tile.h"
 
 #include <algorithm>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 
 namespace ss {
-
-static constexpr uint32_t kInv = 0xFFFFFFFFu;
-static constexpr int kT = 64;  // centers per tile
-static constexpr int kS = 64;  // shared negatives per tile
-static constexpr int kMaxC = 16;  // contexts per center held in registers (window <= 8)
-// 8 waves per workgroup: the LDS tiles (~116 KB at D = 128) allow one
-// workgroup per CU, and the positive-pair loop is a per-wave latency chain
-// (one context-row round trip per center), so 8 waves halve it per wave and
-// double the loads in flight per CU (4 waves: 223 us per 16K-center step)
-static constexpr int kNW = 8;
-static constexpr int kWG = 64 * kNW;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float softplus(float x) {
-  return fmaxf(x, 0.f) + __logf(1.f + __expf(-fabsf(x)));
-}
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + __expf(-x)); }
-
-// 32x32 C/D map of v_mfma_f32_32x32x* (cdna_hip_programming.md §3):
-// col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-__device__ __forceinline__ int mrow(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 template <int D>
 __global__ __launch_bounds__(kWG) void k_w2v_sgns(const uint32_t* __restrict__ inv_c,
@@ -185,15 +166,7 @@ __global__ __launch_bounds__(kWG) void k_w2v_sgns(const uint32_t* __restrict__ i
       atomicAdd(ugrad + (long long)dst * D + col, v);  // lanes 0-31 / 32-63: two 128-B rows
     }
   }
-  for (int o = 32; o > 0; o >>= 1) loss += __shfl_down(loss, o, 64);
-  if (lane == 0) red[w] = loss;
-  __syncthreads();
-  if (tid == 0 && loss_sum) {
-    float tot = 0.f;
-#pragma unroll
-    for (int i = 0; i < kNW; ++i) tot += red[i];
-    ctr_addf(loss_sum, tot);
-  }
+  w2v_block_sums(loss, red, loss_sum);
 }
 
 // ---------------------------------------------------------------------------
@@ -205,14 +178,7 @@ __global__ __launch_bounds__(kWG) void k_w2v_sgns(const uint32_t* __restrict__ i
 // 16-B aligned fragments, rows spread over the banks) the tile needs 77 KB,
 // two workgroups per CU.  The positive pairs stay fp32: each wave reads its
 // centers' rows from global (L2-hot) next to the context rows.
-// Lane map (cdna_hip_programming.md §3): lane l (r = l&31, h = l>>5) holds
-// A[r][8h + j] and B[8h + j][r], j = 0..7; C/D as the fp32 form (mrow).
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ unsigned short f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);  // round to nearest even (finite inputs)
-  return (unsigned short)(u >> 16);
-}
+// Lane map and k-loops: w2v_tile.h.
 
 template <int D>
 struct W2vBf16Smem {
@@ -253,12 +219,8 @@ __global__ __launch_bounds__(kWG, 4) void k_w2v_sgns_bf16(
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f), n = v;
       if (rc[r] != kInv) v = *reinterpret_cast<const float4*>(uvals + (long long)rc[r] * D + d);
       if (rn[r] != kInv) n = *reinterpret_cast<const float4*>(uvals + (long long)rn[r] * D + d);
-      const uint2 pv = make_uint2(f2bf(v.x) | ((uint32_t)f2bf(v.y) << 16),
-                                  f2bf(v.z) | ((uint32_t)f2bf(v.w) << 16));
-      const uint2 pn = make_uint2(f2bf(n.x) | ((uint32_t)f2bf(n.y) << 16),
-                                  f2bf(n.z) | ((uint32_t)f2bf(n.w) << 16));
-      *reinterpret_cast<uint2*>(Vb + r * PB + d) = pv;
-      *reinterpret_cast<uint2*>(Nb + r * PB + d) = pn;
+      *reinterpret_cast<uint2*>(Vb + r * PB + d) = pack_bf16x4(v);
+      *reinterpret_cast<uint2*>(Nb + r * PB + d) = pack_bf16x4(n);
     }
     for (int e = tid; e < kT * P; e += kWG) Gv[e] = 0.f;
     __syncthreads();
@@ -267,13 +229,7 @@ __global__ __launch_bounds__(kWG, 4) void k_w2v_sgns_bf16(
     // ---- S = V·Nᵀ: wave w < 4 owns quadrant (w>>1, w&1)
     if (w < 4) {
       const int i0 = (w >> 1) * 32, j0 = (w & 1) * 32;
-      f32x16 acc = {};
-#pragma unroll
-      for (int k0 = 0; k0 < D; k0 += 16) {
-        const bf16x8 a = *reinterpret_cast<const bf16x8*>(Vb + (i0 + r32) * PB + k0 + 8 * h);
-        const bf16x8 b = *reinterpret_cast<const bf16x8*>(Nb + (j0 + r32) * PB + k0 + 8 * h);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-      }
+      const f32x16 acc = mfma_abt<D>(Vb, PB, i0, Nb, PB, j0, r32, h);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = i0 + mrow(r, lane), col = j0 + r32;
@@ -372,15 +328,7 @@ __global__ __launch_bounds__(kWG, 4) void k_w2v_sgns_bf16(
     }
     __syncthreads();  // the next tile overwrites the LDS tiles
   }
-  for (int o = 32; o > 0; o >>= 1) loss += __shfl_down(loss, o, 64);
-  if (lane == 0) red[w] = loss;
-  __syncthreads();
-  if (tid == 0 && loss_sum) {
-    float tot = 0.f;
-#pragma unroll
-    for (int i = 0; i < kNW; ++i) tot += red[i];
-    ctr_addf(loss_sum, tot);
-  }
+  w2v_block_sums(loss, red, loss_sum);
 }
 
 // ---------------------------------------------------------------------------
@@ -463,8 +411,6 @@ __global__ __launch_bounds__(256) void k_w2v_gen(uint64_t seed, long long base, 
 // once (96 row atomics per tile) instead of once per pair (640 at W = 5 in
 // the pairs layout), and the batch carries B + 2W context keys instead of
 // 2W·B: the dedup, pull and apply of a step shrink with it.
-static constexpr int kWU = 96;  // window rows per tile: 64 + 2W (W <= 15), 3 x 32
-
 template <int D>
 struct W2vWinSmem {
   static constexpr int PB = D + 8;     // bf16 row stride of the V / U / N tiles
@@ -493,8 +439,7 @@ __global__ __launch_bounds__(kWG, 4) void k_w2v_win_bf16(
   __shared__ int32_t mw[kWU];
   __shared__ int uany[kWU];
   __shared__ float cwt[kT];  // n_t * K / S
-  constexpr int NW = kNW;
-  __shared__ float red[NW];
+  __shared__ float red[kNW];
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const long long R = (long long)B + 2 * W;
@@ -504,16 +449,8 @@ __global__ __launch_bounds__(kWG, 4) void k_w2v_win_bf16(
   // CUs to the route stream's kernels)
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const long long t0 = (long long)tile * kT;  // first center; its run position is t0 + W
-    if (tid < kWU) {  // window row l = run position t0 + l
-      const long long q = t0 + tid;
-      const bool in = tid < kT + 2 * W && q < R;
-      const int32_t m = in ? meta[q] : -1;
-      mw[tid] = m;
-      rw[tid] = m >= 0 ? inv_w[q] : kInv;
-      uany[tid] = 0;
-    } else if (tid < kWU + kS) {
-      rn[tid - kWU] = inv_n[(long long)tile * kS + (tid - kWU)];
-    }
+    w2v_win_index(tid, tile, t0, R, W, meta, inv_w, inv_n, mw, rw, rn);
+    if (tid < kWU) uany[tid] = 0;
     __syncthreads();
     if (tid < kT) {  // center t sits at window row t + W
       const int32_t mc = mw[tid + W];
@@ -526,45 +463,17 @@ __global__ __launch_bounds__(kWG, 4) void k_w2v_win_bf16(
       npairs += (float)n;
     }
     __syncthreads();
-    // rows -> bf16 tiles (V, U, N are consecutive rows of stride PB).  Every
-    // load of the thread is issued before the first LDS store (one memory
-    // round trip per tile instead of one per loop trip: the loop form
-    // serialised 14 dependent gathers per thread at D = 128).  A center row
-    // without pairs (rc = kInv) stays zero: its G+ and G- rows are zero.
-    {
-      constexpr int NE = (kT + kWU + kS) * (D / 4), PER = (NE + (64 * NW) - 1) / (64 * NW);
-      float4 v[PER];
-#pragma unroll
-      for (int i = 0; i < PER; ++i) {
-        const int e = tid + i * (64 * NW), r = e / (D / 4), d = 4 * (e - r * (D / 4));
-        const uint32_t id = e >= NE ? kInv : r < kT ? rc[r] : r < kT + kWU ? rw[r - kT] : rn[r - kT - kWU];
-        v[i] = id != kInv ? *reinterpret_cast<const float4*>(uvals + (long long)id * D + d)
-                          : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int i = 0; i < PER; ++i) {
-        const int e = tid + i * (64 * NW), r = e / (D / 4), d = 4 * (e - r * (D / 4));
-        if (e < NE)
-          *reinterpret_cast<uint2*>(smem16 + r * PB + d) =
-              make_uint2(f2bf(v[i].x) | ((uint32_t)f2bf(v[i].y) << 16),
-                         f2bf(v[i].z) | ((uint32_t)f2bf(v[i].w) << 16));
-      }
-    }
+    // rows -> bf16 tiles (V, U, N are consecutive rows of stride PB).  A center
+    // row without pairs (rc = kInv) stays zero: its G+ and G- rows are zero.
+    w2v_stage_rows<D, kT, kWU, kS>(smem16, uvals, tid, rc, rw, rn);
     __syncthreads();
 
     const int r32 = lane & 31, h = lane >> 5;
     // ---- scores: 6 tiles of S+ (2 x 3) and 4 of S- (2 x 2)
-    for (int k = w; k < 10; k += NW) {
+    for (int k = w; k < 10; k += kNW) {
       const bool pos = k < 6;
       const int ti = pos ? k / 3 : (k - 6) >> 1, tj = pos ? k % 3 : (k - 6) & 1;
-      const unsigned short* Bm = pos ? Ub : Nb;
-      f32x16 acc = {};
-#pragma unroll
-      for (int k0 = 0; k0 < D; k0 += 16) {
-        const bf16x8 a = *reinterpret_cast<const bf16x8*>(Vb + (ti * 32 + r32) * PB + k0 + 8 * h);
-        const bf16x8 b = *reinterpret_cast<const bf16x8*>(Bm + (tj * 32 + r32) * PB + k0 + 8 * h);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-      }
+      const f32x16 acc = mfma_abt<D>(Vb, PB, ti * 32, pos ? Ub : Nb, PB, tj * 32, r32, h);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = ti * 32 + mrow(r, lane), col = tj * 32 + r32;
@@ -587,7 +496,7 @@ __global__ __launch_bounds__(kWG, 4) void k_w2v_win_bf16(
     }
     __syncthreads();
     // ---- gradients: gV (2 x TJ tiles), gU (3 x TJ), gN (2 x TJ)
-    for (int tt = w; tt < 7 * TJ; tt += NW) {
+    for (int tt = w; tt < 7 * TJ; tt += kNW) {
       const int kind = tt < 2 * TJ ? 0 : (tt < 5 * TJ ? 1 : 2);
       const int q = tt - (kind == 0 ? 0 : (kind == 1 ? 2 * TJ : 5 * TJ));
       const int ti = q / TJ, tj = q % TJ;
@@ -659,19 +568,7 @@ __global__ __launch_bounds__(kWG, 4) void k_w2v_win_bf16(
     }
     __syncthreads();  // the next tile overwrites the LDS tiles
   }
-  for (int o = 32; o > 0; o >>= 1) loss += __shfl_down(loss, o, 64);
-  if (lane == 0) red[w] = loss;
-  __syncthreads();
-  if (tid == 0 && loss_sum) {
-    float tot = 0.f;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) tot += red[i];
-    ctr_addf(loss_sum, tot);
-  }
-  if (w == 0 && pair_sum) {  // centers' pair counts live in wave 0 (tid < kT)
-    for (int o = 32; o > 0; o >>= 1) npairs += __shfl_down(npairs, o, 64);
-    if (lane == 0) ctr_addf(pair_sum, npairs);  // valid positive pairs
-  }
+  w2v_block_sums(loss, red, loss_sum, npairs, pair_sum);  // npairs: valid positive pairs
 }
 
 // ---------------------------------------------------------------------------
@@ -719,8 +616,6 @@ struct W2vCbowSmem {
       sizeof(unsigned short) * ((size_t)(kWU + kT + kS) * PB + (size_t)kT * GB);
 };
 
-__device__ __forceinline__ float bf2f(unsigned short b) { return __uint_as_float((uint32_t)b << 16); }
-
 template <int D>
 __global__ __launch_bounds__(kWG, 4) void k_w2v_cbow_bf16(
     const uint32_t* __restrict__ inv_c, const uint32_t* __restrict__ inv_w,
@@ -753,15 +648,7 @@ __global__ __launch_bounds__(kWG, 4) void k_w2v_cbow_bf16(
   float loss = 0.f, ntrained = 0.f;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const long long t0 = (long long)tile * kT;  // first center; its run position is t0 + W
-    if (tid < kWU) {
-      const long long q = t0 + tid;
-      const bool in = tid < kT + 2 * W && q < R;
-      const int32_t m = in ? meta[q] : -1;
-      mw[tid] = m;
-      rw[tid] = m >= 0 ? inv_w[q] : kInv;
-    } else if (tid < kWU + kS) {
-      rn[tid - kWU] = inv_n[(long long)tile * kS + (tid - kWU)];
-    }
+    w2v_win_index(tid, tile, t0, R, W, meta, inv_w, inv_n, mw, rw, rn);
     __syncthreads();
     if (tid < kT) {  // center t sits at window row t + W
       const int32_t m = mw[tid + W];
@@ -782,27 +669,8 @@ __global__ __launch_bounds__(kWG, 4) void k_w2v_cbow_bf16(
           any |= w2v_pair_ok(mc[t], mq, tid - (t + W)) ? 1 : 0;
       uany[tid] = any;
     }
-    // rows -> bf16 tiles (X, C, N are consecutive rows of stride PB), every
-    // load issued before the first LDS store: one memory round trip per tile
-    {
-      constexpr int NE = (kWU + kT + kS) * (D / 4), PER = (NE + kWG - 1) / kWG;
-      float4 v[PER];
-#pragma unroll
-      for (int i = 0; i < PER; ++i) {
-        const int e = tid + i * kWG, r = e / (D / 4), d = 4 * (e - r * (D / 4));
-        const uint32_t id = e >= NE ? kInv : r < kWU ? rw[r] : r < kWU + kT ? rc[r - kWU] : rn[r - kWU - kT];
-        v[i] = id != kInv ? *reinterpret_cast<const float4*>(uvals + (long long)id * D + d)
-                          : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int i = 0; i < PER; ++i) {
-        const int e = tid + i * kWG, r = e / (D / 4), d = 4 * (e - r * (D / 4));
-        if (e < NE)
-          *reinterpret_cast<uint2*>(smem16 + r * PB + d) =
-              make_uint2(f2bf(v[i].x) | ((uint32_t)f2bf(v[i].y) << 16),
-                         f2bf(v[i].z) | ((uint32_t)f2bf(v[i].w) << 16));
-      }
-    }
+    // rows -> bf16 tiles (X, C, N are consecutive rows of stride PB)
+    w2v_stage_rows<D, kWU, kT, kS>(smem16, uvals, tid, rw, rc, rn);
     __syncthreads();
 
     // ---- H = diag(1/n)·(M·X): only the k-blocks the band of row tile oi reaches
@@ -834,13 +702,7 @@ __global__ __launch_bounds__(kWG, 4) void k_w2v_cbow_bf16(
     // ---- scores: S- on waves 0..3 (2 x 2 tiles), s+ on waves 4..7
     if (w < 4) {
       const int ti = w >> 1, tj = w & 1;
-      f32x16 acc = {};
-#pragma unroll
-      for (int k0 = 0; k0 < D; k0 += 16) {
-        const bf16x8 a = *reinterpret_cast<const bf16x8*>(Hb + (ti * 32 + r32) * PB + k0 + 8 * h);
-        const bf16x8 b = *reinterpret_cast<const bf16x8*>(Nb + (tj * 32 + r32) * PB + k0 + 8 * h);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-      }
+      const f32x16 acc = mfma_abt<D>(Hb, PB, ti * 32, Nb, PB, tj * 32, r32, h);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = ti * 32 + mrow(r, lane), col = tj * 32 + r32;
@@ -966,19 +828,7 @@ __global__ __launch_bounds__(kWG, 4) void k_w2v_cbow_bf16(
     }
     __syncthreads();  // the next tile overwrites the LDS tiles
   }
-  for (int o = 32; o > 0; o >>= 1) loss += __shfl_down(loss, o, 64);
-  if (lane == 0) red[w] = loss;
-  __syncthreads();
-  if (tid == 0 && loss_sum) {
-    float tot = 0.f;
-#pragma unroll
-    for (int i = 0; i < kNW; ++i) tot += red[i];
-    ctr_addf(loss_sum, tot);
-  }
-  if (w == 0 && pair_sum) {  // the centers' flags live in wave 0 (tid < kT)
-    for (int o = 32; o > 0; o >>= 1) ntrained += __shfl_down(ntrained, o, 64);
-    if (lane == 0) ctr_addf(pair_sum, ntrained);  // trained centers
-  }
+  w2v_block_sums(loss, red, loss_sum, ntrained, pair_sum);  // ntrained: trained centers
 }
 
 // CBOW reverses the namespaces of a window-layout batch: the run positions
@@ -1689,6 +1539,18 @@ static void smem_attr_once(size_t bytes) {
   (void)done;
 }
 
+// Calls f(std::integral_constant<int, D>) for the run-time D the kernels are
+// instantiated for; any other D throws the launcher's message `err`.
+template <class F>
+static void with_dim(int D, const char* err, F&& f) {
+  switch (D) {
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    case 64: f(std::integral_constant<int, 64>{}); break;
+    case 128: f(std::integral_constant<int, 128>{}); break;
+    default: throw_error(err);
+  }
+}
+
 template <int D>
 static void launch_w2v_bf16(int tiles, const uint32_t* inv_c, const uint32_t* inv_x,
                             const uint32_t* inv_n, int B, int C, float neg_scale,
@@ -1712,37 +1574,20 @@ void launch_w2v_sgns(const uint32_t* inv_c, const uint32_t* inv_x, const uint32_
   if (C < 1 || C > kMaxC) throw_error("w2v_sgns: contexts per center must be in [1,16]");
   const int tiles = (B + kT - 1) / kT;
   if (bf16) {
-    switch (D) {
-#define SS_W2VB_CASE(DD)                                                                     \
-  case DD:                                                                                   \
-    launch_w2v_bf16<DD>(tiles, inv_c, inv_x, inv_n, B, C, neg_scale, uvals, ugrad,    \
-                        loss_sum, st);                                                       \
-    break;
-      SS_W2VB_CASE(32)
-      SS_W2VB_CASE(64)
-      SS_W2VB_CASE(128)
-#undef SS_W2VB_CASE
-      default:
-        throw_error("w2v_sgns: D must be 32, 64 or 128");
-    }
+    with_dim(D, "w2v_sgns: D must be 32, 64 or 128", [&](auto d) {
+      launch_w2v_bf16<d.value>(tiles, inv_c, inv_x, inv_n, B, C, neg_scale, uvals, ugrad, loss_sum,
+                               st);
+    });
     check_launch("k_w2v_sgns_bf16");
     return;
   }
   const size_t sm = w2v_smem_bytes(D);
-  switch (D) {
-#define SS_W2V_CASE(DD)                                                                     \
-  case DD:                                                                                  \
-    smem_attr_once<k_w2v_sgns<DD>>(sm);                                                     \
-    hipLaunchKernelGGL(k_w2v_sgns<DD>, dim3(tiles), dim3(kWG), sm, st, inv_c, inv_x, inv_n, B, C, \
-                       neg_scale, uvals, ugrad, loss_sum);                                  \
-    break;
-    SS_W2V_CASE(32)
-    SS_W2V_CASE(64)
-    SS_W2V_CASE(128)
-#undef SS_W2V_CASE
-    default:
-      throw_error("w2v_sgns: D must be 32, 64 or 128");
-  }
+  with_dim(D, "w2v_sgns: D must be 32, 64 or 128", [&](auto d) {
+    constexpr int DD = d.value;
+    smem_attr_once<k_w2v_sgns<DD>>(sm);
+    hipLaunchKernelGGL(k_w2v_sgns<DD>, dim3(tiles), dim3(kWG), sm, st, inv_c, inv_x, inv_n, B, C,
+                       neg_scale, uvals, ugrad, loss_sum);
+  });
   check_launch("k_w2v_sgns");
 }
 
@@ -1947,48 +1792,32 @@ void launch_w2v_oreduce(const uint32_t* items, long long n, const uint32_t* ord,
   if (gnc && pp_items() == 2) {
     // two items per half-wave: half the grid (s and s + nh per half-wave)
     const int g2 = (int)std::max<long long>((n + 15) / 16, acc ? 64 : 1);
-    switch (D) {
-#define SS_W2VO2(DD)                                                                            \
-  case DD:                                                                                      \
-    if (pp_qf() == 4)                                                                           \
-      hipLaunchKernelGGL((k_w2v_oreduce_pp2<DD, 4>), dim3(g2), dim3(256), 0, st, it, n, ord,    \
-                         ograd, ugrad, reinterpret_cast<const float2*>(gnc), negbase, uvals,    \
-                         acc, acc_out, acc_n, tv, slots, opv);                                  \
-    else                                                                                        \
-      hipLaunchKernelGGL((k_w2v_oreduce_pp2<DD, 2>), dim3(g2), dim3(256), 0, st, it, n, ord,    \
-                         ograd, ugrad, reinterpret_cast<const float2*>(gnc), negbase, uvals,    \
-                         acc, acc_out, acc_n, tv, slots, opv);                                  \
-    break;
-      SS_W2VO2(32)
-      SS_W2VO2(64)
-      SS_W2VO2(128)
-#undef SS_W2VO2
-      default:
-        throw_error("w2v_oreduce: D must be 32, 64 or 128");
-    }
+    with_dim(D, "w2v_oreduce: D must be 32, 64 or 128", [&](auto d) {
+      constexpr int DD = d.value;
+      if (pp_qf() == 4)
+        hipLaunchKernelGGL((k_w2v_oreduce_pp2<DD, 4>), dim3(g2), dim3(256), 0, st, it, n, ord,
+                           ograd, ugrad, reinterpret_cast<const float2*>(gnc), negbase, uvals,
+                           acc, acc_out, acc_n, tv, slots, opv);
+      else
+        hipLaunchKernelGGL((k_w2v_oreduce_pp2<DD, 2>), dim3(g2), dim3(256), 0, st, it, n, ord,
+                           ograd, ugrad, reinterpret_cast<const float2*>(gnc), negbase, uvals,
+                           acc, acc_out, acc_n, tv, slots, opv);
+    });
     check_launch("k_w2v_oreduce_pp2");
     return;
   }
-  switch (D) {
-#define SS_W2VO_CASE(DD)                                                                      \
-  case DD:                                                                                    \
-    if (gnc)                                                                                  \
-      hipLaunchKernelGGL((k_w2v_oreduce<DD, true>), dim3(grid), dim3(256), 0, st, it, n, ord,  \
-                         ograd, otail, B, W, ntiles, ugrad,                                    \
-                         reinterpret_cast<const float2*>(gnc), negbase, uvals, acc, acc_out,   \
-                         acc_n, tv, slots, opv, early_slot());                                 \
-    else                                                                                      \
-      hipLaunchKernelGGL((k_w2v_oreduce<DD, false>), dim3(grid), dim3(256), 0, st, it, n, ord, \
-                         ograd, otail, B, W, ntiles, ugrad, nullptr, 0ll, nullptr, acc,        \
-                         acc_out, acc_n, tv, slots, opv, early_slot());                        \
-    break;
-    SS_W2VO_CASE(32)
-    SS_W2VO_CASE(64)
-    SS_W2VO_CASE(128)
-#undef SS_W2VO_CASE
-    default:
-      throw_error("w2v_oreduce: D must be 32, 64 or 128");
-  }
+  with_dim(D, "w2v_oreduce: D must be 32, 64 or 128", [&](auto d) {
+    constexpr int DD = d.value;
+    if (gnc)
+      hipLaunchKernelGGL((k_w2v_oreduce<DD, true>), dim3(grid), dim3(256), 0, st, it, n, ord,
+                         ograd, otail, B, W, ntiles, ugrad,
+                         reinterpret_cast<const float2*>(gnc), negbase, uvals, acc, acc_out,
+                         acc_n, tv, slots, opv, early_slot());
+    else
+      hipLaunchKernelGGL((k_w2v_oreduce<DD, false>), dim3(grid), dim3(256), 0, st, it, n, ord,
+                         ograd, otail, B, W, ntiles, ugrad, nullptr, 0ll, nullptr, acc,
+                         acc_out, acc_n, tv, slots, opv, early_slot());
+  });
   check_launch("k_w2v_oreduce");
 }
 
@@ -1998,26 +1827,19 @@ void launch_w2v_win(const uint32_t* inv_c, const uint32_t* inv_w, const uint32_t
                     hipStream_t st, float* ograd, float* otail) {
   if (B <= 0) return;
   if (W < 1 || W > kW2vMaxWindow) throw_error("w2v_win: window must be in [1, 15]");
+  if (ograd && !otail && B > kT) throw_error("w2v_win: occurrence rows need the tail buffer");
   const int tiles = (B + kT - 1) / kT;
   const int grid = w2v_tile_grid(tiles, ograd == nullptr);
   // 8 waves per tile: 16 (1024 threads) ran the tile alone 29.6 -> 23.1 us
   // but the step 0.083 -> 0.093 ms (its registers fill the CU's SIMDs and
   // nothing else runs beside it)
-  switch (D) {
-#define SS_W2VW_CASE(DD)                                                                     \
-  case DD:                                                                                   \
-    smem_attr_once<k_w2v_win_bf16<DD>>(W2vWinSmem<DD>::bytes);                               \
-    hipLaunchKernelGGL(k_w2v_win_bf16<DD>, dim3(grid), dim3(512), W2vWinSmem<DD>::bytes, st,     \
-                       inv_c, inv_w, inv_n, meta, B, W, neg_per_pair, uvals, ugrad, loss_sum,  \
-                       pair_sum, ograd, otail);                                                \
-    break;
-    SS_W2VW_CASE(32)
-    SS_W2VW_CASE(64)
-    SS_W2VW_CASE(128)
-#undef SS_W2VW_CASE
-    default:
-      throw_error("w2v_win: D must be 32, 64 or 128");
-  }
+  with_dim(D, "w2v_win: D must be 32, 64 or 128", [&](auto d) {
+    constexpr int DD = d.value;
+    smem_attr_once<k_w2v_win_bf16<DD>>(W2vWinSmem<DD>::bytes);
+    hipLaunchKernelGGL(k_w2v_win_bf16<DD>, dim3(grid), dim3(kWG), W2vWinSmem<DD>::bytes, st,
+                       inv_c, inv_w, inv_n, meta, B, W, neg_per_pair, uvals, ugrad, loss_sum,
+                       pair_sum, ograd, otail);
+  });
   check_launch("k_w2v_win_bf16");
 }
 
@@ -2030,21 +1852,13 @@ void launch_w2v_cbow(const uint32_t* inv_c, const uint32_t* inv_w, const uint32_
   if (ograd && !otail && B > kT) throw_error("w2v_cbow: occurrence rows need the tail buffer");
   const int tiles = (B + kT - 1) / kT;
   const int grid = w2v_tile_grid(tiles, ograd == nullptr);
-  switch (D) {
-#define SS_W2VC_CASE(DD)                                                                     \
-  case DD:                                                                                   \
-    smem_attr_once<k_w2v_cbow_bf16<DD>>(W2vCbowSmem<DD>::bytes);                             \
-    hipLaunchKernelGGL(k_w2v_cbow_bf16<DD>, dim3(grid), dim3(kWG), W2vCbowSmem<DD>::bytes, st,  \
-                       inv_c, inv_w, inv_n, meta, B, W, neg_per_center, uvals, ugrad,         \
-                       loss_sum, pair_sum, ograd, otail);                                      \
-    break;
-    SS_W2VC_CASE(32)
-    SS_W2VC_CASE(64)
-    SS_W2VC_CASE(128)
-#undef SS_W2VC_CASE
-    default:
-      throw_error("w2v_cbow: D must be 32, 64 or 128");
-  }
+  with_dim(D, "w2v_cbow: D must be 32, 64 or 128", [&](auto d) {
+    constexpr int DD = d.value;
+    smem_attr_once<k_w2v_cbow_bf16<DD>>(W2vCbowSmem<DD>::bytes);
+    hipLaunchKernelGGL(k_w2v_cbow_bf16<DD>, dim3(grid), dim3(kWG), W2vCbowSmem<DD>::bytes, st,
+                       inv_c, inv_w, inv_n, meta, B, W, neg_per_center, uvals, ugrad,
+                       loss_sum, pair_sum, ograd, otail);
+  });
   check_launch("k_w2v_cbow_bf16");
 }
 
@@ -2075,33 +1889,25 @@ void launch_w2v_pp(const uint32_t* inv_c, const uint32_t* inv_w, const uint32_t*
   if (K < 1 || K > kPpMaxK) throw_error("w2v_pp: negatives per pair must be in [1, 16]");
   if (2 * W * K > 64 * kPpIdx) throw_error("w2v_pp: 2W x K must be <= 512");
   const long long Rn = (long long)B + 2 * W;
-  switch (D) {
-#define SS_W2VP_CASE(DD)                                                                       \
-  case DD:                                                                                     \
-    if (K <= 5 && pp_stages() == 3)                                                            \
-      hipLaunchKernelGGL((k_w2v_pp<DD, 5, 3>), dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st,  \
-                         inv_c, inv_w, inv_n, meta, B, W, K, uvals, ograd, gpair, loss_sum,     \
-                         pair_sum, reinterpret_cast<float2*>(gnc));                             \
-    else if (K <= 5 && pp_stages() > 3)                                                        \
-      hipLaunchKernelGGL((k_w2v_pp<DD, 5, 4>), dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st,  \
-                         inv_c, inv_w, inv_n, meta, B, W, K, uvals, ograd, gpair, loss_sum,     \
-                         pair_sum, reinterpret_cast<float2*>(gnc));                             \
-    else                                                                                       \
-      hipLaunchKernelGGL(k_w2v_pp16<DD>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st,       \
-                         inv_c, inv_w, inv_n, meta, B, W, K, uvals, ograd, gpair, loss_sum,     \
-                         pair_sum, reinterpret_cast<float2*>(gnc));                             \
-    check_launch("k_w2v_pp");                                                                  \
-    hipLaunchKernelGGL(k_w2v_ppctx<DD>, dim3((unsigned)((Rn + 3) / 4)), dim3(256), 0, st,       \
-                       inv_c, gpair, B, W, uvals, ograd);                                      \
-    check_launch("k_w2v_ppctx");                                                               \
-    break;
-    SS_W2VP_CASE(32)
-    SS_W2VP_CASE(64)
-    SS_W2VP_CASE(128)
-#undef SS_W2VP_CASE
-    default:
-      throw_error("w2v_pp: D must be 32, 64 or 128");
-  }
+  with_dim(D, "w2v_pp: D must be 32, 64 or 128", [&](auto d) {
+    constexpr int DD = d.value;
+    if (K <= 5 && pp_stages() == 3)
+      hipLaunchKernelGGL((k_w2v_pp<DD, 5, 3>), dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st,
+                         inv_c, inv_w, inv_n, meta, B, W, K, uvals, ograd, gpair, loss_sum,
+                         pair_sum, reinterpret_cast<float2*>(gnc));
+    else if (K <= 5 && pp_stages() > 3)
+      hipLaunchKernelGGL((k_w2v_pp<DD, 5, 4>), dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st,
+                         inv_c, inv_w, inv_n, meta, B, W, K, uvals, ograd, gpair, loss_sum,
+                         pair_sum, reinterpret_cast<float2*>(gnc));
+    else
+      hipLaunchKernelGGL(k_w2v_pp16<DD>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st,
+                         inv_c, inv_w, inv_n, meta, B, W, K, uvals, ograd, gpair, loss_sum,
+                         pair_sum, reinterpret_cast<float2*>(gnc));
+    check_launch("k_w2v_pp");
+    hipLaunchKernelGGL(k_w2v_ppctx<DD>, dim3((unsigned)((Rn + 3) / 4)), dim3(256), 0, st,
+                       inv_c, gpair, B, W, uvals, ograd);
+    check_launch("k_w2v_ppctx");
+  });
 }
 
 void launch_w2v_stream_gen(uint64_t seed, long long base, int B, int W, int L, long long nneg,

@@ -149,6 +149,30 @@ def test_w2v_window_tile_matches_reference(dev, D, W, B):
     _assert_w2v_within_bound(f"window tile D {D} W {W} B {B}", G, o, loss.sum().item())
 
 
+@pytest.mark.parametrize("name", ["w2v_win", "w2v_cbow"])
+def test_w2v_window_tiles_refuse_occurrence_rows_without_tail(dev, name):
+    """More than one tile (B = 65) storing occurrence rows shares 2W window
+    rows between neighbouring tiles: both window launchers refuse a missing
+    tail buffer before anything is launched."""
+    from swiftsnails_amd._native import hip
+
+    B, W, D, S = 65, 2, 32, 64
+    R, tiles = B + 2 * W, 2
+    nrows = B + R + tiles * S
+    inv = torch.arange(nrows, dtype=torch.int32, device=dev)
+    meta = torch.full((R,), (1 << 4) | W, dtype=torch.int32, device=dev)
+    u, g, og = (torch.zeros((nrows, D), device=dev) for _ in range(3))
+    loss, pairs = torch.zeros(256 * 32, device=dev), torch.zeros(256 * 32, device=dev)
+    p = inv.data_ptr()
+    with pytest.raises(RuntimeError, match=f"{name}: occurrence rows need the tail buffer"):
+        getattr(hip(), name)(p, p + B * 4, p + (B + R) * 4, meta.data_ptr(), B, W, D, 5 / S,
+                             u.data_ptr(), g.data_ptr(), loss.data_ptr(), pairs.data_ptr(),
+                             torch.cuda.current_stream().cuda_stream, ograd=og.data_ptr(),
+                             otail=0)
+    torch.cuda.synchronize()
+    assert not og.any() and not g.any()
+
+
 @pytest.mark.parametrize("D,W,K,B", [(32, 2, 3, 70), (64, 5, 5, 128), (128, 5, 5, 200),
                                      (128, 15, 16, 40), (64, 5, 6, 70), (32, 3, 11, 70)])
 def test_w2v_per_pair_negatives_match_reference(dev, D, W, K, B):
