@@ -84,11 +84,7 @@ static constexpr int kBdTargetDist = 3072;
 // layout, 512..4096 (the servers' sub-bucket count follows it,
 // server.hip srv_sub_buckets)
 int bd_target_dist() {
-  static const int v = [] {
-    const char* e = std::getenv("SS_BD_TARGET_DIST");
-    const int x = e ? std::atoi(e) : kBdTargetDist;
-    return x < 512 ? 512 : (x > 4096 ? 4096 : x);
-  }();
+  static const int v = std::min(4096, std::max(512, env_int("SS_BD_TARGET_DIST", kBdTargetDist)));
   return v;
 }
 // SS_BD_TARGET (one rank): occurrences per bucket, 1024..3584 (A/B: larger
@@ -104,11 +100,7 @@ int bd_target_dist() {
 // process: engines of either kind can coexist.
 static constexpr int kBdRecLayout = 1 << 16;
 static int bd_target(int nranks, bool rec) {
-  static const int one = [] {
-    const char* e = std::getenv("SS_BD_TARGET");
-    const int v = e ? std::atoi(e) : kBdTarget;
-    return v < 1024 ? 1024 : (v > 3584 ? 3584 : v);
-  }();
+  static const int one = std::min(3584, std::max(1024, env_int("SS_BD_TARGET", kBdTarget)));
   if (nranks > 1 && rec) return std::max(256, kBdTarget / nranks);
   return nranks > 1 ? bd_target_dist() : one;
 }
@@ -956,20 +948,12 @@ __global__ __launch_bounds__(RT) void k_bd_reduce(const uint32_t* __restrict__ b
 // SS_BD_ROCC: occurrences per thread in flight in k_bd_reduce (2, 4 or 8);
 // SS_BD_RT: its workgroup size (256, 512, 1024)
 static int bd_rocc() {
-  static const int v = [] {
-    const char* e = std::getenv("SS_BD_ROCC");
-    const int x = e ? std::atoi(e) : 4;
-    return x == 2 || x == 8 ? x : 4;
-  }();
-  return v;
+  static const int x = env_int("SS_BD_ROCC", 4);
+  return x == 2 || x == 8 ? x : 4;
 }
 static int bd_rt() {
-  static const int v = [] {
-    const char* e = std::getenv("SS_BD_RT");
-    const int x = e ? std::atoi(e) : 1024;
-    return x == 256 || x == 512 ? x : 1024;
-  }();
-  return v;
+  static const int x = env_int("SS_BD_RT", 1024);
+  return x == 256 || x == 512 ? x : 1024;
 }
 // one launch of k_bd_reduce over P buckets at the (SS_BD_RT, SS_BD_ROCC)
 // shape: (1024, 2 / 4), (512, 2 / 4 / 8), (256, 2); others fall back to (1024, 4)
@@ -1288,10 +1272,11 @@ int launch_bd_dedup(const uint64_t* keys, long long n, RouteSpec rs, long long u
   // (SS_BD_CS), scatter (SS_BD_CT).  Measured in the pipelined bench, where
   // the route stream shares the chip with the pull/forward kernels
   auto wg_env = [](const char* name, int def) {
-    const char* e = std::getenv(name);
-    const int v = e ? std::atoi(e) : def;
+    const int v = env_int(name, def);
     return (v == 256 || v == 512 || v == 1024) ? v : def;
   };
+  // f(CT) for one of those workgroup sizes
+  auto with_wg = [](int wg, auto&& f) { with_value_or<1024, 256, 512>(wg, f); };
   static const int ct = wg_env("SS_BD_CT", 1024);
   // count: 1024 threads.  (256 on the N>1 path paid while its rounds pulled
   // ahead — the count then ran beside the server pull and waited for 16 free
@@ -1308,76 +1293,49 @@ int launch_bd_dedup(const uint64_t* keys, long long n, RouteSpec rs, long long u
   }();
   uint32_t* wacc = narrow_ok ? S + L.wacc : nullptr;
   uint32_t* wfin = S + L.wfin;
-#define SS_BD_CT_DISPATCH(ct, KERNEL, ...)                                                    \
-  switch (ct) {                                                                               \
-    case 256: hipLaunchKernelGGL(KERNEL<256>, dim3(L.nch), dim3(256), lds, st, __VA_ARGS__); break; \
-    case 512: hipLaunchKernelGGL(KERNEL<512>, dim3(L.nch), dim3(512), lds, st, __VA_ARGS__); break; \
-    default: hipLaunchKernelGGL(KERNEL<1024>, dim3(L.nch), dim3(1024), lds, st, __VA_ARGS__);     \
-  }
-#define SS_BD_CT_DISPATCH2(ct, RW, KERNEL, ...)                                                  \
-  switch (ct) {                                                                               \
-    case 256: hipLaunchKernelGGL((KERNEL<256, RW>), dim3(L.nch), dim3(256), lds, st, __VA_ARGS__); break; \
-    case 512: hipLaunchKernelGGL((KERNEL<512, RW>), dim3(L.nch), dim3(512), lds, st, __VA_ARGS__); break; \
-    default: hipLaunchKernelGGL((KERNEL<1024, RW>), dim3(L.nch), dim3(1024), lds, st, __VA_ARGS__);     \
-  }
-  SS_BD_CT_DISPATCH(cnt, k_bd_count, keys, n, rs, L.Pd, L.P, L.chunk, S + L.hist, ucount, wacc);
+  with_wg(cnt, [&](auto c) {
+    hipLaunchKernelGGL(k_bd_count<c.value>, dim3(L.nch), dim3(c.value), lds, st, keys, n, rs,
+                       L.Pd, L.P, L.chunk, S + L.hist, ucount, wacc);
+  });
   RecLay rl{};
   if (spj) rl = RecLay{ucap, L.Pd, ucount, S + L.ubase, S + L.unum, S};
   check_launch("k_bd_count");
-  switch (cs) {
-#define SS_BD_CS_CASE(CS)                                                                      \
-  case CS:                                                                                     \
-    hipLaunchKernelGGL(k_bd_colscan<CS>, dim3((L.P + 63) / 64), dim3(CS), 0, st, S + L.hist,   \
-                       L.nch, L.P, S + L.btot, S + L.bstart, S + L.ctr, wacc, wfin, rl);       \
-    break;
-    SS_BD_CS_CASE(256)
-    SS_BD_CS_CASE(512)
-    SS_BD_CS_CASE(1024)
-#undef SS_BD_CS_CASE
-  }
+  with_wg(cs, [&](auto c) {
+    hipLaunchKernelGGL(k_bd_colscan<c.value>, dim3((L.P + 63) / 64), dim3(c.value), 0, st,
+                       S + L.hist, L.nch, L.P, S + L.btot, S + L.bstart, S + L.ctr, wacc, wfin,
+                       rl);
+  });
   check_launch("k_bd_colscan");
   // the LDS-sorted scatter (12- / 8-byte records): the largest tile whose
   // workgroup fits the LDS (a P of up to ~16K buckets takes 2048-key tiles)
-  static const bool sorted = [] {
-    const char* e = std::getenv("SS_BD_SORT");
-    return !(e && e[0] == '0');
-  }();
+  static const bool sorted = env_flag("SS_BD_SORT", true);
   auto s_lds = [&](int kt) { return sizeof(unsigned int) * (2 * (size_t)L.P + 1 + 2 * (size_t)kt * 1024); };
   const size_t kLdsMax = 160 * 1024 - 256;
   // SS_BD_SKT: the largest keys-per-thread tile to try (16 measured best)
-  static const int skt_max = [] {
-    const char* e = std::getenv("SS_BD_SKT");
-    return e ? std::atoi(e) : 16;
-  }();
+  static const int skt_max = env_int("SS_BD_SKT", 16);
   int skt = 0;
   for (int kt = 16; kt >= 2 && !skt; kt /= 2)
     if (kt <= skt_max && s_lds(kt) <= kLdsMax) skt = kt;
   if (sorted && skt && L.P < 65536) {
     if (L.chunk % 1024) throw_error("bdedup: chunk not a multiple of 1024");
-    switch (skt) {
-#define SS_BD_S_CASE(KT)                                                                          \
-  case KT: {                                                                                      \
-    static const bool attr = (check_hip(hipFuncSetAttribute((const void*)k_bd_scatter_s<KT>,       \
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                            (int)kLdsMax),                        \
-                                        "k_bd_scatter_s LDS"),                                    \
-                              true);                                                              \
-    (void)attr;                                                                                   \
-    hipLaunchKernelGGL(k_bd_scatter_s<KT>, dim3(L.nch), dim3(1024), s_lds(KT), st, keys, n, rs,  \
-                       L.Pd, L.P, L.chunk, S + L.hist, S + L.bstart, pos_of, bkt, rec, wfin,      \
-                       spj ? ukeys : nullptr, spj, pj);                                           \
-  } break;
-      SS_BD_S_CASE(16)
-      SS_BD_S_CASE(8)
-      SS_BD_S_CASE(4)
-      SS_BD_S_CASE(2)
-#undef SS_BD_S_CASE
-    }
+    with_value_or<2, 16, 8, 4>(skt, [&](auto k) {  // skt is one of the four
+      constexpr int KT = k.value;
+      static const bool attr = (check_hip(hipFuncSetAttribute((const void*)k_bd_scatter_s<KT>,
+                                                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                              (int)kLdsMax),
+                                          "k_bd_scatter_s LDS"),
+                                true);
+      (void)attr;
+      hipLaunchKernelGGL(k_bd_scatter_s<KT>, dim3(L.nch), dim3(1024), s_lds(KT), st, keys, n, rs,
+                         L.Pd, L.P, L.chunk, S + L.hist, S + L.bstart, pos_of, bkt, rec, wfin,
+                         spj ? ukeys : nullptr, spj, pj);
+    });
   } else
-    SS_BD_CT_DISPATCH2(ct, 3, k_bd_scatter, keys, n, rs, L.Pd, L.P, L.chunk, S + L.hist,
-                       S + L.bstart, pj, pos_of, bkt, rec, wfin, spj ? ukeys : nullptr, spj)
-#undef SS_BD_CT_DISPATCH
-#undef SS_BD_CT_DISPATCH2
+    with_wg(ct, [&](auto c) {
+      hipLaunchKernelGGL((k_bd_scatter<c.value, 3>), dim3(L.nch), dim3(c.value), lds, st, keys, n,
+                         rs, L.Pd, L.P, L.chunk, S + L.hist, S + L.bstart, pj, pos_of, bkt, rec,
+                         wfin, spj ? ukeys : nullptr, spj);
+    });
   check_launch("k_bd_scatter");
   if (spj) return rs.rbits;  // record exchange: the servers dedup
   // place: unique keys straight into the per-destination send segments
@@ -1475,37 +1433,41 @@ static int rec_grid(long long cap, int nd) {
 
 void launch_rec_grad(const unsigned long long* ucount, int nd, long long gap, const uint32_t* spj,
                      const float* gs, const float* xval, int F, float* grec, hipStream_t st,
-                     float* lacc, float* lacc_out, int lacc_n, int skip) {
+                     const LossHandoff& loss, int skip) {
   if (nd < 1 || nd > kRecMaxDest || gap < 1 || F < 1) throw_error("rec_grad: bad layout");
-  if (lacc && (!lacc_out || lacc_n <= 0)) throw_error("rec_grad: loss hand-off needs its output");
+  loss.check("rec_grad: loss hand-off needs its output");
   if (skip >= nd) throw_error("rec_grad: skipped destination out of range");
   // the grid covers the ranges walked: none at one rank with its own skipped
   // (the launch then only hands the loss off)
   int grid = rec_grid(gap, skip >= 0 ? nd - 1 : nd);
   // ... and at least one thread per accumulator word for the hand-off (one
   // workgroup walking 8192 words took 16 us of dependent load -> store)
-  if (lacc) grid = std::max(grid, (lacc_n + 255) / 256);
+  if (loss.acc) grid = std::max(grid, (loss.n + 255) / 256);
   hipLaunchKernelGGL(k_rec_grad, dim3(grid), dim3(256), 0, st, ucount, nd, gap, spj, gs, xval, F,
-                     grec, lacc, lacc_out, lacc_n, skip);
+                     grec, loss.acc, loss.out, loss.n, skip);
   check_launch("k_rec_grad");
 }
 
-void launch_bd_fill_occ(long long n, int nranks, const uint32_t* scratch, const uint32_t* luid,
-                        const float* uvals, float* occ, int osi, hipStream_t st, int ndest,
-                        const uint32_t* pj) {
-  if (n <= 0) return;
+BucketView bd_view(long long n, int nranks, int ndest, const uint32_t* scratch,
+                   const uint32_t* pj, const uint32_t* luid, const uint64_t* bkeys) {
+  if (n <= 0) return {};
   const BdLayout L = bd_layout(n, nranks, ndest);
-  hipLaunchKernelGGL(k_bd_fill_occ<512>, dim3(L.P), dim3(512), 0, st, scratch + L.bstart,
-                     scratch + L.ubase, scratch + L.unum, luid, uvals, occ, osi, pj, SelfSeg{});
+  return {L.P, scratch + L.bstart, scratch + L.ubase, scratch + L.unum, pj, luid, bkeys};
+}
+
+void launch_bd_fill_occ(const BucketView& v, const float* uvals, float* occ, int osi,
+                        hipStream_t st, SelfSeg self) {
+  if (v.P <= 0) return;
+  hipLaunchKernelGGL(k_bd_fill_occ<512>, dim3(v.P), dim3(512), 0, st, v.bstart, v.ubase, v.unum,
+                     v.luid, uvals, occ, osi, v.pj, self);
   check_launch("k_bd_fill_occ");
 }
 
-void launch_bd_unplace(long long n, int nranks, const uint32_t* scratch, const float* src,
-                       float* dst, int dim, hipStream_t st, int ndest) {
-  if (n <= 0) return;
-  const BdLayout L = bd_layout(n, nranks, ndest);
-  hipLaunchKernelGGL(k_bd_unplace, dim3(L.P), dim3(256), 0, st, scratch + L.bstart,
-                     scratch + L.unum, scratch + L.ubase, src, dst, dim);
+void launch_bd_unplace(const BucketView& v, const float* src, float* dst, int dim,
+                       hipStream_t st) {
+  if (v.P <= 0) return;
+  hipLaunchKernelGGL(k_bd_unplace, dim3(v.P), dim3(256), 0, st, v.bstart, v.unum, v.ubase, src,
+                     dst, dim);
   check_launch("k_bd_unplace");
 }
 
@@ -1515,84 +1477,39 @@ static bool scalar_pair_rule(int kind, const DevTable& t) {
   return (kind == kOptAdaGrad && !t.zn) || (kind == kOptFTRLzn && t.zn);
 }
 
-void launch_bd_reduce(long long n, int nranks, const uint32_t* scratch, const uint32_t* pj,
-                      const uint32_t* luid, const float* gs, const float* xval, int F,
+void check_fused_scalar(const char* who, const FusedApply& f, bool compact_ids, int osi) {
+  const DevTable* t = f.t;
+  if (f.on() && (!t || !f.op || (compact_ids && osi) || t->bf16 ||
+                 !scalar_pair_rule(f.op->kind, *t) || t->dim != 1 || t->width != 2 ||
+                 t->row_off % 8 != 0 || t->stride % 8 != 0))
+    throw_error(std::string(who) + ": fused apply needs scalar AdaGrad or FTRL (z, n) rows" +
+                (compact_ids ? " and compact ids" : ""));
+  if (f.bkeys && (!f.on() || !f.snap || t->stride != 16 || t->key_off != 8 || t->row_off != 0))
+    throw_error(std::string(who) + ": slot stores with keys need a snapshot merge into " +
+                (compact_ids ? "16-byte " : "") + "[w|h|key] slots");
+}
+
+void launch_bd_reduce(const BucketView& v, const float* gs, const float* xval, int F,
                       float* ugrad, hipStream_t st, int osi, const uint8_t* usingle,
-                      const DevTable* t, const long long* slots, const float* snap,
-                      const OptParams* op, int ndest, int slot32, float* lacc, float* lacc_out,
-                      int lacc_n, const uint64_t* bkeys) {
-  if (n <= 0) return;
-  if (lacc && (!lacc_out || lacc_n <= 0)) throw_error("bd_reduce: loss hand-off needs its output");
+                      const FusedApply& fa, const LossHandoff& loss, SelfSeg self, bool srv) {
+  if (v.P <= 0) return;
+  loss.check("bd_reduce: loss hand-off needs its output");
   if (F < 1) throw_error("bd_reduce: F must be >= 1");
-  // slot32: `slots` holds 4-byte indices (k_pull_unique_bk's slot32 form)
-  const int* s32 = slot32 ? reinterpret_cast<const int*>(slots) : nullptr;
-  if (slot32) slots = nullptr;
-  DevTable tv{};
-  OptParams opv{};
-  if (slots || s32) {
-    if (!t || !op || osi || t->bf16 || !scalar_pair_rule(op->kind, *t) || t->dim != 1 ||
-        t->width != 2 || t->row_off % 8 != 0 || t->stride % 8 != 0)
-      throw_error("bd_reduce: fused apply needs scalar AdaGrad or FTRL (z, n) rows and compact ids");
-    tv = *t;
-    opv = *op;
-  }
-  if (bkeys && (!(slots || s32) || !snap || t->stride != 16 || t->key_off != 8 || t->row_off != 0))
-    throw_error("bd_reduce: slot stores with keys need a snapshot merge into 16-byte [w|h|key] slots");
-  const float2* sn = reinterpret_cast<const float2*>(snap);
-  const BdLayout L = bd_layout(n, nranks, ndest);
-  const uint32_t* S = scratch;
+  check_fused_scalar(srv ? "bd_reduce_p" : "bd_reduce", fa, !srv, osi);
   // workgroup shape: SS_BD_RT / SS_BD_ROCC (bd_reduce_launch)
-  bd_reduce_launch(L.P, st, S + L.bstart, S + L.ubase, S + L.unum, pj, luid, gs, xval, F, ugrad,
-                   osi, usingle, tv, slots, sn, opv, SelfSeg{}, s32, lacc, lacc_out, lacc_n, bkeys);
-  check_launch("k_bd_reduce");
-}
-
-// explicit-layout forms (server.hip: the server's merge of received keys has
-// its own bucket arrays instead of a BdLayout scratch)
-void launch_bd_reduce_p(int P, const uint32_t* bstart, const uint32_t* ubase, const uint32_t* unum,
-                        const uint32_t* pj, const uint32_t* luid, const float* gs, int F,
-                        float* ugrad, const DevTable* t, const long long* slots,
-                        const float* snap, const OptParams* op, hipStream_t st, SelfSeg self,
-                        int slot32, const uint64_t* bkeys) {
-  if (P <= 0) return;
-  DevTable tv{};
-  OptParams opv{};
-  const int* s32 = slot32 ? reinterpret_cast<const int*>(slots) : nullptr;
-  if (slot32) slots = nullptr;
-  if (slots || s32) {
-    if (!t || !op || t->bf16 || !scalar_pair_rule(op->kind, *t) || t->dim != 1 ||
-        t->width != 2 || t->row_off % 8 != 0 || t->stride % 8 != 0)
-      throw_error("bd_reduce_p: fused apply needs scalar AdaGrad or FTRL (z, n) rows");
-    tv = *t;
-    opv = *op;
-  }
-  if (bkeys && (!(slots || s32) || !snap || t->stride != 16 || t->key_off != 8 || t->row_off != 0))
-    throw_error("bd_reduce_p: slot stores with keys need a snapshot merge into [w|h|key] slots");
-  bd_reduce_launch(P, st, bstart, ubase, unum, pj, luid, gs, static_cast<const float*>(nullptr), F,
-                   ugrad, 0, static_cast<const uint8_t*>(nullptr), tv, slots,
-                   reinterpret_cast<const float2*>(snap), opv, self, s32,
-                   static_cast<float*>(nullptr), static_cast<float*>(nullptr), 0, bkeys);
-  check_launch("k_bd_reduce_p");
-}
-
-void launch_bd_fill_occ_p(int P, const uint32_t* bstart, const uint32_t* ubase,
-                          const uint32_t* unum, const uint32_t* luid, const float* uvals,
-                          float* occ, const uint32_t* pj, hipStream_t st, SelfSeg self) {
-  if (P <= 0) return;
-  hipLaunchKernelGGL(k_bd_fill_occ<512>, dim3(P), dim3(512), 0, st, bstart, ubase, unum, luid,
-                     uvals, occ, 0, pj, self);
-  check_launch("k_bd_fill_occ_p");
+  bd_reduce_launch(v.P, st, v.bstart, v.ubase, v.unum, v.pj, v.luid, gs, xval, F, ugrad, osi,
+                   usingle, fa.table(), fa.slots, reinterpret_cast<const float2*>(fa.snap),
+                   fa.rule(), self, fa.slots32, loss.acc, loss.out, loss.n, fa.bkeys);
+  check_launch(srv ? "k_bd_reduce_p" : "k_bd_reduce");
 }
 
 long long bd_fm_ovf_words(long long n) { return n / kFmOcc + 2; }
 
-void launch_bd_reduce_fm(long long n, int nranks, const uint32_t* scratch, const uint32_t* pj,
-                         const uint32_t* luid, const float* gs, const float* gss, int F, int dim,
-                         const float* uvals, float* ugrad, hipStream_t st, uint32_t* ovf,
-                         int ndest) {
-  if (n <= 0) return;
-  const BdLayout L = bd_layout(n, nranks, ndest);
-  const uint32_t* S = scratch;
+void launch_bd_reduce_fm(const BucketView& v, long long n, const float* gs, const float* gss,
+                         int F, int dim, const float* uvals, float* ugrad, hipStream_t st,
+                         uint32_t* ovf) {
+  if (v.P <= 0) return;
+  const char* bad_dim = "bd_reduce_fm: dim must be 1+K with K in {1,4,8,16}";
   // default: sorted lists (no float atomics) + LDS-atomic form for overflow
   // buckets; ovf = {count, bucket ids} scratch of bd_fm_ovf_words(n) words
   static const bool sorted = [] {
@@ -1602,39 +1519,19 @@ void launch_bd_reduce_fm(long long n, int nranks, const uint32_t* scratch, const
   if (ovf && sorted) {
     const int novf = (int)(n / kFmOcc) + 1;  // an overflow bucket holds > kFmOcc keys
     check_hip(hipMemsetAsync(ovf, 0, sizeof(uint32_t), st), "fm ovf count");
-    switch (dim) {
-#define SS_BDFMS_CASE(DD)                                                                      \
-  case DD:                                                                                     \
-    hipLaunchKernelGGL(k_bd_reduce_fm_sorted<DD>, dim3(L.P), dim3(1024), 0, st, S + L.bstart,  \
-                       S + L.ubase, S + L.unum, pj, luid, gs, gss, F, uvals, ugrad, ovf);      \
-    hipLaunchKernelGGL(k_bd_reduce_fm<DD>, dim3(novf), dim3(1024), 0, st, S + L.bstart,         \
-                       S + L.ubase, S + L.unum, pj, luid, gs, gss, F, uvals, ugrad, ovf);      \
-    break;
-      SS_BDFMS_CASE(2)
-      SS_BDFMS_CASE(5)
-      SS_BDFMS_CASE(9)
-      SS_BDFMS_CASE(17)
-#undef SS_BDFMS_CASE
-      default:
-        throw_error("bd_reduce_fm: dim must be 1+K with K in {1,4,8,16}");
-    }
+    with_value<2, 5, 9, 17>(dim, bad_dim, [&](auto d) {
+      hipLaunchKernelGGL(k_bd_reduce_fm_sorted<d.value>, dim3(v.P), dim3(1024), 0, st, v.bstart,
+                         v.ubase, v.unum, v.pj, v.luid, gs, gss, F, uvals, ugrad, ovf);
+      hipLaunchKernelGGL(k_bd_reduce_fm<d.value>, dim3(novf), dim3(1024), 0, st, v.bstart,
+                         v.ubase, v.unum, v.pj, v.luid, gs, gss, F, uvals, ugrad, ovf);
+    });
     check_launch("k_bd_reduce_fm_sorted");
     return;
   }
-  switch (dim) {
-#define SS_BDFM_CASE(DD)                                                                       \
-  case DD:                                                                                     \
-    hipLaunchKernelGGL(k_bd_reduce_fm<DD>, dim3(L.P), dim3(1024), 0, st, S + L.bstart,        \
-                       S + L.ubase, S + L.unum, pj, luid, gs, gss, F, uvals, ugrad, nullptr);   \
-    break;
-    SS_BDFM_CASE(2)
-    SS_BDFM_CASE(5)
-    SS_BDFM_CASE(9)
-    SS_BDFM_CASE(17)
-#undef SS_BDFM_CASE
-    default:
-      throw_error("bd_reduce_fm: dim must be 1+K with K in {1,4,8,16}");
-  }
+  with_value<2, 5, 9, 17>(dim, bad_dim, [&](auto d) {
+    hipLaunchKernelGGL(k_bd_reduce_fm<d.value>, dim3(v.P), dim3(1024), 0, st, v.bstart, v.ubase,
+                       v.unum, v.pj, v.luid, gs, gss, F, uvals, ugrad, nullptr);
+  });
   check_launch("k_bd_reduce_fm");
 }
 

@@ -21,4 +21,23 @@ struct BdIndex {
   }
 };
 
+// The bucketed dedup's output as the bucket kernels walk it, one workgroup
+// per bucket b (a BdLayout scratch through bd_view, or a server merge's own
+// arrays).  Host-side only: the kernels take the arrays as separate
+// __restrict__ arguments, and no kernel takes them all.
+struct BucketView {
+  int P = 0;                         // buckets
+  const uint32_t* bstart = nullptr;  // [P + 1], by bucket: its first position
+  const uint32_t* ubase = nullptr;   // [P], by bucket: unique id of its first distinct key
+  const uint32_t* unum = nullptr;    // [P], by bucket: its distinct keys
+  const uint32_t* pj = nullptr;      // by position: the occurrence's index in the call's keys
+  const uint32_t* luid = nullptr;    // by position: the key's id inside its bucket (~0: none)
+  const uint64_t* bkeys = nullptr;   // by bstart[b] + in-bucket id: the distinct keys, staged
+};
+// ... as launch_srv_dedup writes it
+struct BucketViewOut {
+  uint32_t *bstart, *ubase, *unum, *pj, *luid;
+  uint64_t* bkeys;
+};
+
 }  // namespace ss

@@ -55,6 +55,23 @@ static BdIndex make_bdindex(const std::vector<uintptr_t>& v) {
                  P<const uint32_t>(v[3])};
 }
 
+// the bucket view a caller passes as integer pointers; each binding maps its
+// own (historical) argument order onto these names once, here
+static BucketView make_view(int P_, uintptr_t bstart, uintptr_t ubase, uintptr_t unum,
+                            uintptr_t pj = 0, uintptr_t luid = 0, uintptr_t bkeys = 0) {
+  return BucketView{P_, P<const uint32_t>(bstart), P<const uint32_t>(ubase),
+                    P<const uint32_t>(unum), P<const uint32_t>(pj), P<const uint32_t>(luid),
+                    P<const uint64_t>(bkeys)};
+}
+// ... and of a BdLayout scratch (bdedup.hip bd_view)
+static BucketView scratch_view(long long n, int nranks, int ndest, uintptr_t scratch, uintptr_t pj,
+                               uintptr_t luid, uintptr_t bkeys = 0) {
+  return bd_view(n, nranks, ndest, P<const uint32_t>(scratch), P<const uint32_t>(pj),
+                 P<const uint32_t>(luid), P<const uint64_t>(bkeys));
+}
+static const DevTable* ptr(const std::optional<DevTable>& t) { return t ? &*t : nullptr; }
+static const OptParams* ptr(const std::optional<OptParams>& op) { return op ? &*op : nullptr; }
+
 void bind_xgmi(py::module_& m);  // xgmi.hip
 namespace ss {
 void bind_round_engine(py::module_& m);  // round_engine.cpp
@@ -147,10 +164,9 @@ PYBIND11_MODULE(_ss_hip, m) {
                              uintptr_t ubase, int P_, uintptr_t slots, uintptr_t out,
                              const InitParams& ip, uintptr_t size_ctr, uintptr_t err, int G,
                              uintptr_t st, uintptr_t snap, int slot32) {
-    launch_pull_unique_bk(t, P<const uint64_t>(bkeys), P<const uint32_t>(bstart),
-                          P<const uint32_t>(unum), P<const uint32_t>(ubase), P_,
-                          P<long long>(slots), P<float>(out), ip, P<unsigned long long>(size_ctr),
-                          P<int>(err), G, S(st), P<float>(snap), slot32);
+    launch_pull_unique_bk(t, make_view(P_, bstart, ubase, unum, 0, 0, bkeys), P<long long>(slots),
+                          P<float>(out), ip, P<unsigned long long>(size_ctr), P<int>(err), G,
+                          S(st), P<float>(snap), slot32);
   }, py::arg("t"), py::arg("bkeys"), py::arg("bstart"), py::arg("unum"), py::arg("ubase"),
      py::arg("P"), py::arg("slots"), py::arg("out"), py::arg("ip"), py::arg("size_ctr"),
      py::arg("err"), py::arg("G"), py::arg("st"), py::arg("snap") = 0, py::arg("slot32") = 0);
@@ -158,10 +174,9 @@ PYBIND11_MODULE(_ss_hip, m) {
                             uintptr_t ubase, int P_, uintptr_t slots32, uintptr_t out,
                             uintptr_t snap, const InitParams& ip, uintptr_t size_ctr,
                             uintptr_t err, uintptr_t st, uintptr_t luid, uintptr_t occ) {
-    launch_pull_claim_bk(t, P<const uint64_t>(bkeys), P<const uint32_t>(bstart),
-                         P<const uint32_t>(unum), P<const uint32_t>(ubase), P_, P<int>(slots32),
+    launch_pull_claim_bk(t, make_view(P_, bstart, ubase, unum, 0, luid, bkeys), P<int>(slots32),
                          P<float>(out), P<float>(snap), ip, P<unsigned long long>(size_ctr),
-                         P<int>(err), S(st), P<const uint32_t>(luid), P<float>(occ));
+                         P<int>(err), S(st), P<float>(occ));
   }, py::arg("t"), py::arg("bkeys"), py::arg("bstart"), py::arg("unum"), py::arg("ubase"),
      py::arg("P"), py::arg("slots32"), py::arg("out"), py::arg("snap"), py::arg("ip"),
      py::arg("size_ctr"), py::arg("err"), py::arg("st"), py::arg("luid") = 0,
@@ -170,8 +185,7 @@ PYBIND11_MODULE(_ss_hip, m) {
   m.def("commit_claims", [](const DevTable& t, uintptr_t bkeys, uintptr_t bstart, uintptr_t unum,
                             uintptr_t ubase, int P_, uintptr_t slots32, uintptr_t snap,
                             uintptr_t st, uintptr_t err) {
-    launch_commit_claims(t, P<const uint64_t>(bkeys), P<const uint32_t>(bstart),
-                         P<const uint32_t>(unum), P<const uint32_t>(ubase), P_,
+    launch_commit_claims(t, make_view(P_, bstart, ubase, unum, 0, 0, bkeys),
                          P<const int>(slots32), P<const float>(snap), S(st), P<int>(err));
   }, py::arg("t"), py::arg("bkeys"), py::arg("bstart"), py::arg("unum"), py::arg("ubase"),
      py::arg("P"), py::arg("slots32"), py::arg("snap"), py::arg("st"), py::arg("err") = 0);
@@ -265,7 +279,7 @@ PYBIND11_MODULE(_ss_hip, m) {
                        uintptr_t acc_out, int acc_n, int skip) {
     launch_rec_grad(P<const unsigned long long>(ucount), nd, gap, P<const uint32_t>(spj),
                     P<const float>(gs), P<const float>(xval), F, P<float>(grec), S(st),
-                    P<float>(acc), P<float>(acc_out), acc_n, skip);
+                    LossHandoff{P<float>(acc), P<float>(acc_out), acc_n}, skip);
   }, py::arg("ucount"), py::arg("nd"), py::arg("gap"), py::arg("spj"), py::arg("gs"),
      py::arg("xval"), py::arg("F"), py::arg("grec"), py::arg("st"), py::arg("acc") = 0,
      py::arg("acc_out") = 0, py::arg("acc_n") = 0, py::arg("skip") = -1);
@@ -274,12 +288,12 @@ PYBIND11_MODULE(_ss_hip, m) {
                         int osi, uintptr_t usingle, std::optional<DevTable> t, uintptr_t slots,
                         uintptr_t snap, std::optional<OptParams> op, int ndest, int slot32,
                         uintptr_t acc, uintptr_t acc_out, int acc_n, uintptr_t bkeys) {
-    launch_bd_reduce(n, nranks, P<const uint32_t>(scratch), P<const uint32_t>(pj),
-                     P<const uint32_t>(luid), P<const float>(gs), P<const float>(xval), F,
-                     P<float>(ugrad), S(st), osi, P<const uint8_t>(usingle),
-                     t ? &*t : nullptr, P<const long long>(slots), P<const float>(snap),
-                     op ? &*op : nullptr, ndest, slot32, P<float>(acc), P<float>(acc_out), acc_n,
-                     P<const uint64_t>(bkeys));
+    launch_bd_reduce(scratch_view(n, nranks, ndest, scratch, pj, luid), P<const float>(gs),
+                     P<const float>(xval), F, P<float>(ugrad), S(st), osi,
+                     P<const uint8_t>(usingle),
+                     fused_apply(ptr(t), ptr(op), P<const void>(slots), slot32,
+                                 P<const float>(snap), P<const uint64_t>(bkeys)),
+                     LossHandoff{P<float>(acc), P<float>(acc_out), acc_n});
   }, py::arg("n"), py::arg("nranks"), py::arg("scratch"), py::arg("pj"), py::arg("luid"),
      py::arg("gs"), py::arg("xval"), py::arg("F"), py::arg("ugrad"), py::arg("st"),
      py::arg("osi") = 0, py::arg("usingle") = 0, py::arg("t") = py::none(), py::arg("slots") = 0,
@@ -288,8 +302,8 @@ PYBIND11_MODULE(_ss_hip, m) {
      py::arg("bkeys") = 0);
   m.def("bd_unplace", [](long long n, int nranks, uintptr_t scratch, uintptr_t src, uintptr_t dst,
                          int dim, uintptr_t st, int ndest) {
-    launch_bd_unplace(n, nranks, P<const uint32_t>(scratch), P<const float>(src), P<float>(dst),
-                      dim, S(st), ndest);
+    launch_bd_unplace(scratch_view(n, nranks, ndest, scratch, 0, 0), P<const float>(src),
+                      P<float>(dst), dim, S(st));
   }, py::arg("n"), py::arg("nranks"), py::arg("scratch"), py::arg("src"), py::arg("dst"),
      py::arg("dim"), py::arg("st"), py::arg("ndest") = 0);
   m.def("route_keys", [](uintptr_t keys, long long n, uintptr_t frag_map, int frag_num,
@@ -399,9 +413,8 @@ PYBIND11_MODULE(_ss_hip, m) {
   m.def("bd_fill_occ", [](long long n, int nranks, uintptr_t scratch, uintptr_t luid,
                           uintptr_t uvals, uintptr_t occ, int osi, uintptr_t st, int ndest,
                           uintptr_t pj) {
-    launch_bd_fill_occ(n, nranks, P<const uint32_t>(scratch), P<const uint32_t>(luid),
-                       P<const float>(uvals), P<float>(occ), osi, S(st), ndest,
-                       P<const uint32_t>(pj));
+    launch_bd_fill_occ(scratch_view(n, nranks, ndest, scratch, pj, luid), P<const float>(uvals),
+                       P<float>(occ), osi, S(st));
   }, py::arg("n"), py::arg("nranks"), py::arg("scratch"), py::arg("luid"), py::arg("uvals"),
      py::arg("occ"), py::arg("osi"), py::arg("st"), py::arg("ndest") = 0, py::arg("pj") = 0);
   // server-side merge of a round's received keys (server.hip)
@@ -412,8 +425,9 @@ PYBIND11_MODULE(_ss_hip, m) {
                         uintptr_t luid, uintptr_t bkeys, uintptr_t ubase, uintptr_t unum,
                         uintptr_t ucount, uintptr_t err, uintptr_t st, uintptr_t roff) {
     launch_srv_dedup(P<const uint64_t>(rkeys), P<const uint32_t>(rbase), P<const uint32_t>(rnum),
-                     cap, nsrc, Pd, m, me, P<uint32_t>(cnt), P<uint32_t>(bstart), P<uint32_t>(pj),
-                     P<uint32_t>(luid), P<uint64_t>(bkeys), P<uint32_t>(ubase), P<uint32_t>(unum),
+                     cap, nsrc, Pd, m, me, P<uint32_t>(cnt),
+                     BucketViewOut{P<uint32_t>(bstart), P<uint32_t>(ubase), P<uint32_t>(unum),
+                                   P<uint32_t>(pj), P<uint32_t>(luid), P<uint64_t>(bkeys)},
                      P<unsigned long long>(ucount), P<uint32_t>(err), S(st),
                      P<const uint32_t>(roff));
   }, py::arg("rkeys"), py::arg("rbase"), py::arg("rnum"), py::arg("cap"), py::arg("nsrc"),
@@ -422,14 +436,11 @@ PYBIND11_MODULE(_ss_hip, m) {
      py::arg("err"), py::arg("st"), py::arg("roff") = 0);
   m.def("srv_fill", [](int Pn, uintptr_t bstart, uintptr_t ubase, uintptr_t unum, uintptr_t pj,
                        uintptr_t luid, uintptr_t rows, uintptr_t out, int D, uintptr_t st) {
+    const BucketView v = make_view(Pn, bstart, ubase, unum, pj, luid);
     if (D == 1)
-      launch_bd_fill_occ_p(Pn, P<const uint32_t>(bstart), P<const uint32_t>(ubase),
-                           P<const uint32_t>(unum), P<const uint32_t>(luid),
-                           P<const float>(rows), P<float>(out), P<const uint32_t>(pj), S(st));
+      launch_bd_fill_occ(v, P<const float>(rows), P<float>(out), 0, S(st));
     else
-      launch_srv_fill_rows(Pn, P<const uint32_t>(bstart), P<const uint32_t>(ubase),
-                           P<const uint32_t>(pj), P<const uint32_t>(luid), P<const float>(rows),
-                           P<float>(out), D, S(st));
+      launch_srv_fill_rows(v, P<const float>(rows), P<float>(out), D, S(st));
   });
   // merged gradients per distinct key; with a table the update is fused
   // (scalar rows: from the snapshot (blind store) or read from the row)
@@ -441,18 +452,15 @@ PYBIND11_MODULE(_ss_hip, m) {
     // [row | key] 16-byte slot stores with the buckets' staged keys
     if (D != 1 && (slot32 || bkeys))
       throw std::invalid_argument("srv_merge: slot32 / bkeys are for scalar rows");
+    const BucketView v = make_view(Pn, bstart, ubase, unum, pj, luid);
     if (D == 1)
-      launch_bd_reduce_p(Pn, P<const uint32_t>(bstart), P<const uint32_t>(ubase),
-                         P<const uint32_t>(unum), P<const uint32_t>(pj), P<const uint32_t>(luid),
-                         P<const float>(grads), 1, P<float>(merged), t ? &*t : nullptr,
-                         P<const long long>(slots), P<const float>(snap), op ? &*op : nullptr,
-                         S(st), SelfSeg{}, slot32, P<const uint64_t>(bkeys));
+      launch_bd_reduce(v, P<const float>(grads), nullptr, 1, P<float>(merged), S(st), 0, nullptr,
+                       fused_apply(ptr(t), ptr(op), P<const void>(slots), slot32,
+                                   P<const float>(snap), P<const uint64_t>(bkeys)),
+                       {}, SelfSeg{}, true);
     else
-      launch_srv_merge_rows(Pn, P<const uint32_t>(bstart), P<const uint32_t>(ubase),
-                            P<const uint32_t>(unum), P<const uint32_t>(pj),
-                            P<const uint32_t>(luid), P<const float>(grads), P<float>(merged), D,
-                            S(st), t ? &*t : nullptr, P<const long long>(slots),
-                            op ? &*op : nullptr);
+      launch_srv_merge_rows(v, P<const float>(grads), P<float>(merged), D, S(st),
+                            fused_apply(ptr(t), ptr(op), P<const void>(slots), false, nullptr));
   }, py::arg("P"), py::arg("bstart"), py::arg("ubase"), py::arg("unum"), py::arg("pj"),
      py::arg("luid"), py::arg("grads"), py::arg("merged"), py::arg("D"),
      py::arg("t") = std::nullopt, py::arg("slots") = 0, py::arg("snap") = 0,
@@ -469,9 +477,9 @@ PYBIND11_MODULE(_ss_hip, m) {
                            uintptr_t luid, uintptr_t gs, uintptr_t gss, int F, int dim,
                            uintptr_t uvals, uintptr_t ugrad, uintptr_t st, uintptr_t ovf,
                            int ndest) {
-    launch_bd_reduce_fm(n, nranks, P<const uint32_t>(scratch), P<const uint32_t>(pj),
-                        P<const uint32_t>(luid), P<const float>(gs), P<const float>(gss), F, dim,
-                        P<const float>(uvals), P<float>(ugrad), S(st), P<uint32_t>(ovf), ndest);
+    launch_bd_reduce_fm(scratch_view(n, nranks, ndest, scratch, pj, luid), n, P<const float>(gs),
+                        P<const float>(gss), F, dim, P<const float>(uvals), P<float>(ugrad),
+                        S(st), P<uint32_t>(ovf));
   }, py::arg("n"), py::arg("nranks"), py::arg("scratch"), py::arg("pj"), py::arg("luid"),
      py::arg("gs"), py::arg("gss"), py::arg("F"), py::arg("dim"), py::arg("uvals"),
      py::arg("ugrad"), py::arg("st"), py::arg("ovf") = 0, py::arg("ndest") = 0);
@@ -572,9 +580,8 @@ PYBIND11_MODULE(_ss_hip, m) {
   m.def("w2v_osort", [](int P_, uintptr_t bstart, uintptr_t unum, uintptr_t ubase, uintptr_t pj,
                         uintptr_t luid, uintptr_t ord, uintptr_t items, uintptr_t st,
                         uintptr_t uhot) {
-    launch_w2v_osort(P_, P<const uint32_t>(bstart), P<const uint32_t>(unum),
-                     P<const uint32_t>(ubase), P<const uint32_t>(pj), P<const uint32_t>(luid),
-                     P<uint32_t>(ord), P<uint32_t>(items), S(st), P<uint8_t>(uhot));
+    launch_w2v_osort(make_view(P_, bstart, ubase, unum, pj, luid), P<uint32_t>(ord),
+                     P<uint32_t>(items), S(st), P<uint8_t>(uhot));
   }, py::arg("P"), py::arg("bstart"), py::arg("unum"), py::arg("ubase"), py::arg("pj"),
      py::arg("luid"), py::arg("ord"), py::arg("items"), py::arg("st"), py::arg("uhot") = 0);
   m.def("w2v_oreduce", [](uintptr_t items, long long n, uintptr_t ord, uintptr_t ograd,
@@ -584,9 +591,9 @@ PYBIND11_MODULE(_ss_hip, m) {
                           uintptr_t slots, std::optional<OptParams> op) {
     launch_w2v_oreduce(P<const uint32_t>(items), n, P<const uint32_t>(ord), P<const float>(ograd),
                        P<const float>(otail), B, W, D, P<float>(ugrad), S(st),
-                       P<const float>(gnc), negbase, P<const float>(uvals), P<float>(acc),
-                       P<float>(acc_out), acc_n, t ? &*t : nullptr, P<const long long>(slots),
-                       op ? &*op : nullptr);
+                       P<const float>(gnc), negbase, P<const float>(uvals),
+                       LossHandoff{P<float>(acc), P<float>(acc_out), acc_n},
+                       fused_apply(ptr(t), ptr(op), P<const void>(slots), false, nullptr));
   }, py::arg("items"), py::arg("n"), py::arg("ord"), py::arg("ograd"), py::arg("otail"),
      py::arg("B"), py::arg("W"), py::arg("D"), py::arg("ugrad"), py::arg("st"),
      py::arg("gnc") = 0, py::arg("negbase") = 0, py::arg("uvals") = 0, py::arg("acc") = 0,

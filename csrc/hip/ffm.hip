@@ -218,21 +218,12 @@ void launch_ffm_fwd_bwd(const uint32_t* inv, const float* labels, int B, int F, 
   if (bytes > (size_t)kFfmLdsLimit)
     throw_error("ffm_fwd_bwd: the sample tile needs " + std::to_string(bytes) +
                 " bytes of LDS, over the limit of " + std::to_string(kFfmLdsLimit));
-#define SS_FFM_CASE(KK)                                                                        \
-  case KK:                                                                                     \
-    if (G == 16)                                                                               \
-      ffm_launch<KK, 16>(inv, labels, B, F, LD, bytes, uvals, ugrad, loss_sum, pred, st);      \
-    else if (G == 64)                                                                          \
-      ffm_launch<KK, 64>(inv, labels, B, F, LD, bytes, uvals, ugrad, loss_sum, pred, st);      \
-    else                                                                                       \
-      ffm_launch<KK, 256>(inv, labels, B, F, LD, bytes, uvals, ugrad, loss_sum, pred, st);     \
-    break;
-  switch (K) {
-    SS_FFM_CASE(2)
-    SS_FFM_CASE(4)
-    SS_FFM_CASE(8)
-  }
-#undef SS_FFM_CASE
+  with_value<2, 4, 8>(K, "ffm_fwd_bwd: K must be 2, 4 or 8", [&](auto k) {
+    constexpr int KK = k.value;
+    with_value_or<256, 16, 64>(G, [&](auto g) {
+      ffm_launch<KK, g.value>(inv, labels, B, F, LD, bytes, uvals, ugrad, loss_sum, pred, st);
+    });
+  });
   check_launch("k_ffm_fwd_bwd");
 }
 

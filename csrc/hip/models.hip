@@ -354,20 +354,10 @@ void launch_fm_fwd_g(const uint32_t* inv, const BdIndex& ix, const float* labels
   const int L = group_lanes(F), spb = 256 / L;
   if (L < dim - 1) throw_error("fm_fwd_g: needs F >= K lanes per sample");
   const int blocks = (B + spb - 1) / spb;
-  switch (dim) {
-#define SS_FMG_CASE(DD)                                                                      \
-  case DD:                                                                                   \
-    hipLaunchKernelGGL(k_fm_fwd_g<DD>, dim3(blocks), dim3(256), 0, st, inv, ix, labels, B, F, \
-                       L, uvals, gs, gss, loss_sum, pred);                                   \
-    break;
-    SS_FMG_CASE(2)
-    SS_FMG_CASE(5)
-    SS_FMG_CASE(9)
-    SS_FMG_CASE(17)
-#undef SS_FMG_CASE
-    default:
-      throw_error("fm_fwd_g: dim must be 1+K with K in {1,4,8,16}");
-  }
+  with_value<2, 5, 9, 17>(dim, "fm_fwd_g: dim must be 1+K with K in {1,4,8,16}", [&](auto d) {
+    hipLaunchKernelGGL(k_fm_fwd_g<d.value>, dim3(blocks), dim3(256), 0, st, inv, ix, labels, B, F,
+                       L, uvals, gs, gss, loss_sum, pred);
+  });
   check_launch("k_fm_fwd_g");
 }
 
@@ -378,20 +368,10 @@ void launch_fm_fwd_bwd(const uint32_t* inv, const float* labels, int B, int F, i
   if (F < 2 || F > 256) throw_error("fm_fwd_bwd: F must be in [2,256]");
   const int spb = samples_per_block(F);
   const int blocks = (B + spb - 1) / spb;
-  switch (dim) {
-#define SS_FM_CASE(DD)                                                                       \
-  case DD:                                                                                   \
-    hipLaunchKernelGGL(k_fm_fwd_bwd<DD>, dim3(blocks), dim3(256), 0, st, inv, labels, B, F, uvals, \
-                       ugrad, loss_sum, pred);                                               \
-    break;
-    SS_FM_CASE(2)
-    SS_FM_CASE(5)
-    SS_FM_CASE(9)
-    SS_FM_CASE(17)
-#undef SS_FM_CASE
-    default:
-      throw_error("fm_fwd_bwd: dim must be 1+K with K in {1,4,8,16}");
-  }
+  with_value<2, 5, 9, 17>(dim, "fm_fwd_bwd: dim must be 1+K with K in {1,4,8,16}", [&](auto d) {
+    hipLaunchKernelGGL(k_fm_fwd_bwd<d.value>, dim3(blocks), dim3(256), 0, st, inv, labels, B, F,
+                       uvals, ugrad, loss_sum, pred);
+  });
   check_launch("k_fm_fwd_bwd");
 }
 
@@ -406,8 +386,7 @@ void launch_gen_ctr(uint64_t seed, long long sample_base, int B, int F, long lon
   // R sample groups per workgroup (SS_GEN_R: 1 / 2 / 4 / 8); 8 measured
   // 0.7227-0.7229 vs 0.7266-0.7278 ms per bench step (4), three A/B pairs
   static const int gr = [] {
-    const char* e = std::getenv("SS_GEN_R");
-    const int v = e ? std::atoi(e) : 8;
+    const int v = env_int("SS_GEN_R", 8);
     return (v == 1 || v == 2 || v == 4) ? v : 8;
   }();
   if (gr > 1 && gr * spb <= 256) {

@@ -42,12 +42,14 @@ hipStream_t St(uintptr_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 // device buffers of one ring slot's server merge (engine._ServerSlot)
 struct SrvSlot {
-  uint32_t *cnt = nullptr, *bstart = nullptr, *ubase = nullptr, *unum = nullptr;
-  uint32_t *pj = nullptr, *luid = nullptr;
-  uint64_t* bkeys = nullptr;
+  uint32_t* cnt = nullptr;
+  // the merge's bucket arrays: launch_srv_dedup writes them (v), the pull,
+  // fill and merge kernels of the round walk them (view)
+  BucketViewOut v{};
   long long* slots = nullptr;
   float* snap = nullptr;
   unsigned long long* ucount = nullptr;
+  BucketView view(int P) const { return {P, v.bstart, v.ubase, v.unum, v.pj, v.luid, v.bkeys}; }
 };
 
 // device buffers of one ring slot of the one-GPU path: the pulled rows, their
@@ -174,10 +176,10 @@ class RoundEngine {
                        uintptr_t pj, uintptr_t luid, uintptr_t bkeys, uintptr_t slots,
                        uintptr_t ucount, uintptr_t snap) {
     check_slot(slot);
-    srv_[slot] = {Pt<uint32_t>(cnt),   Pt<uint32_t>(bstart), Pt<uint32_t>(ubase),
-                  Pt<uint32_t>(unum),  Pt<uint32_t>(pj),     Pt<uint32_t>(luid),
-                  Pt<uint64_t>(bkeys), Pt<long long>(slots), Pt<float>(snap),
-                  Pt<unsigned long long>(ucount)};
+    srv_[slot] = {Pt<uint32_t>(cnt),
+                  {Pt<uint32_t>(bstart), Pt<uint32_t>(ubase), Pt<uint32_t>(unum), Pt<uint32_t>(pj),
+                   Pt<uint32_t>(luid), Pt<uint64_t>(bkeys)},
+                  Pt<long long>(slots), Pt<float>(snap), Pt<unsigned long long>(ucount)};
   }
   // the one-GPU ring's buffers of one slot (snap 0: no snapshot pulls)
   void set_local_slot(int slot, uintptr_t uvals, uintptr_t slots, uintptr_t snap) {
@@ -238,19 +240,19 @@ class RoundEngine {
                  uintptr_t luid, uintptr_t occ) {
     const LocalSlot& L = local(slot, take_snap);
     if (view.size() != 4) throw std::invalid_argument("pull_fast: (bkeys, bstart, unum, ubase)");
+    // no pj: the claimed pull's occurrence rows go to the occurrences' positions
+    const BucketView bv{P, Pt<const uint32_t>(view[1]), Pt<const uint32_t>(view[3]),
+                        Pt<const uint32_t>(view[2]), nullptr, Pt<const uint32_t>(luid),
+                        Pt<const uint64_t>(view[0])};
     const uintptr_t uvals = L.uvals, slots = L.slots, snap = take_snap ? L.snap : 0;
     // claim: region-aligned buckets of a region table — LDS-claimed inserts,
     // the fused merge stores the slots (k_pull_claim_bk)
     if (claim)
-      launch_pull_claim_bk(t, Pt<const uint64_t>(view[0]), Pt<const uint32_t>(view[1]),
-                           Pt<const uint32_t>(view[2]), Pt<const uint32_t>(view[3]), P,
-                           Pt<int>(slots), occ ? nullptr : Pt<float>(uvals), Pt<float>(snap), ip,
-                           Pt<unsigned long long>(size_ctr), Pt<int>(err), St(stream),
-                           Pt<const uint32_t>(luid), Pt<float>(occ));
+      launch_pull_claim_bk(t, bv, Pt<int>(slots), occ ? nullptr : Pt<float>(uvals),
+                           Pt<float>(snap), ip, Pt<unsigned long long>(size_ctr), Pt<int>(err),
+                           St(stream), Pt<float>(occ));
     else
-      launch_pull_unique_bk(t, Pt<const uint64_t>(view[0]), Pt<const uint32_t>(view[1]),
-                            Pt<const uint32_t>(view[2]), Pt<const uint32_t>(view[3]), P,
-                            Pt<long long>(slots), Pt<float>(uvals), ip,
+      launch_pull_unique_bk(t, bv, Pt<long long>(slots), Pt<float>(uvals), ip,
                             Pt<unsigned long long>(size_ctr), Pt<int>(err), G, St(stream),
                             Pt<float>(snap), slot32);
     if (ahead) record(kPull, slot, stream, tag);
@@ -292,6 +294,7 @@ class RoundEngine {
       const DevTable& t = *table;
       const InitParams& ip = *init;
       SrvSlot& S = srv_[slot];
+      const BucketView bv = S.view(Pd_ * sub_);
       // snapshot pulls of 16-byte scalar slots in a shard under 2^31 slots
       // store 4-byte slot indices; the push's fused merge reads them back
       srv_s32_[slot] = snap && G == 1 && t.stride == 16 && t.key_off == 8 && t.row_off == 0 &&
@@ -304,18 +307,17 @@ class RoundEngine {
         if (snap || claim || custom_pull)
           throw std::invalid_argument("pull_xgmi: a read-only lookup takes no snapshot / claim / hook");
         srv_s32_[slot] = srv_claim_[slot] = 0;
-        launch_lookup_bk(t, S.bkeys, S.bstart, S.unum, S.ubase, Pd_ * sub_, Pt<float>(svals_), G,
-                         St(ss));
+        launch_lookup_bk(t, bv, Pt<float>(svals_), G, St(ss));
       } else if (srv_claim_[slot]) {
         // scalar rows: the response fill (rows per received position) fused
         // into the claimed pull — the bucket's rows are staged in its LDS
         // (SS_SRV_FILL_FUSED=0: the separate fill kernel)
         const bool fused = dim_ == 1 && !custom_pull && srv_fill_fused();
-        launch_pull_claim_bk(t, S.bkeys, S.bstart, S.unum, S.ubase, Pd_ * sub_,
-                             reinterpret_cast<int*>(S.slots), fused ? nullptr : Pt<float>(svals_),
-                             S.snap, ip, Pt<unsigned long long>(size_ctr), Pt<int>(err), St(ss),
-                             fused ? S.luid : nullptr, fused ? Pt<float>(rvals_) : nullptr,
-                             fused ? S.pj : nullptr, fused ? vals_self(slot) : SelfSeg{});
+        launch_pull_claim_bk(t, bv, reinterpret_cast<int*>(S.slots),
+                             fused ? nullptr : Pt<float>(svals_), S.snap, ip,
+                             Pt<unsigned long long>(size_ctr), Pt<int>(err), St(ss),
+                             fused ? Pt<float>(rvals_) : nullptr,
+                             fused ? vals_self(slot) : SelfSeg{});
         if (fused) {
           fill_and_put(slot, ss, false, true);
           rows_wait(slot, stream, sent, metrics);
@@ -323,9 +325,9 @@ class RoundEngine {
           return;
         }
       } else
-        launch_pull_unique_bk(t, S.bkeys, S.bstart, S.unum, S.ubase, Pd_ * sub_, S.slots,
-                              Pt<float>(svals_), ip, Pt<unsigned long long>(size_ctr), Pt<int>(err),
-                              G, St(ss), snap ? S.snap : nullptr, srv_s32_[slot]);
+        launch_pull_unique_bk(t, bv, S.slots, Pt<float>(svals_), ip,
+                              Pt<unsigned long long>(size_ctr), Pt<int>(err), G, St(ss),
+                              snap ? S.snap : nullptr, srv_s32_[slot]);
       if (custom_pull) return;  // the caller finishes the pull (tensor-code hooks)
       fill_and_put(slot, ss, true);
     } else {
@@ -410,7 +412,7 @@ class RoundEngine {
       const DevTable& t = *table;
       const OptParams& op = *opt;
       SrvSlot& S = srv_[slot];
-      const int Ps = Pd_ * sub_;
+      const BucketView bv = S.view(Pd_ * sub_);
       // every source's gradient rows of the round: the grads mailbox
       const uintptr_t rgrads = ar_[slot][2]->base() + grads_[slot].data;
       SelfSeg sg = self_seg(grads);  // this rank's own gradient rows, in place
@@ -424,22 +426,18 @@ class RoundEngine {
         throw std::logic_error("push_xgmi: a 4-byte-slot pull needs the fused snapshot merge");
       if (srv_claim_[slot] && !(update && scalar_fused && snap))
         throw std::logic_error("push_xgmi: a claimed pull needs the fused snapshot merge");
-      if (update && scalar_fused)
-        launch_bd_reduce_p(Ps, S.bstart, S.ubase, S.unum, S.pj, S.luid, Pt<const float>(rgrads),
-                           1, nullptr, &t, S.slots, snap ? S.snap : nullptr, &op, St(stream), sg,
-                           srv_s32_[slot], srv_claim_[slot] ? S.bkeys : nullptr);
-      else if (dim_ == 1)
-        launch_bd_reduce_p(Ps, S.bstart, S.ubase, S.unum, S.pj, S.luid, Pt<const float>(rgrads),
-                           1, Pt<float>(sgrad_), nullptr, nullptr, nullptr, nullptr, St(stream),
-                           sg);
-      else if (update)
-        launch_srv_merge_rows(Ps, S.bstart, S.ubase, S.unum, S.pj, S.luid,
-                              Pt<const float>(rgrads), nullptr, dim_, St(stream), &t, S.slots,
-                              &op, sg);
+      // the fused update; none: the merged rows go to sgrad
+      FusedApply fa{};
+      if (update)
+        fa = scalar_fused ? fused_apply(&t, &op, S.slots, srv_s32_[slot], snap ? S.snap : nullptr,
+                                        srv_claim_[slot] ? S.v.bkeys : nullptr)
+                          : fused_apply(&t, &op, S.slots, false, nullptr);
+      float* merged = update ? nullptr : Pt<float>(sgrad_);
+      if (dim_ == 1)
+        launch_bd_reduce(bv, Pt<const float>(rgrads), nullptr, 1, merged, St(stream), 0, nullptr,
+                         fa, {}, sg, true);
       else
-        launch_srv_merge_rows(Ps, S.bstart, S.ubase, S.unum, S.pj, S.luid,
-                              Pt<const float>(rgrads), Pt<float>(sgrad_), dim_, St(stream),
-                              nullptr, nullptr, nullptr, sg);
+        launch_srv_merge_rows(bv, Pt<const float>(rgrads), merged, dim_, St(stream), fa, sg);
     }
     if (release) record(kFree, slot, stream, tag);
   }
@@ -482,9 +480,8 @@ class RoundEngine {
     launch_srv_dedup(Pt<const uint64_t>(base + keys_[slot][0].data),
                      Pt<const uint32_t>(base + keys_[slot][1].data),
                      Pt<const uint32_t>(base + keys_[slot][2].data), cap_, nranks_, Pd_, sub_,
-                     rank_, S.cnt, S.bstart, S.pj, S.luid, S.bkeys, S.ubase, S.unum, S.ucount,
-                     Pt<uint32_t>(srv_err_),
-                     St(stream), roff, self_seg(self_keys_[slot]));
+                     rank_, S.cnt, S.v, S.ucount, Pt<uint32_t>(srv_err_), St(stream), roff,
+                     self_seg(self_keys_[slot]));
   }
   // where the server's response rows for this rank's own keys go: its vals
   // arena (same row index), or the record exchange's cached own-row buffer
@@ -506,10 +503,7 @@ class RoundEngine {
   // SS_XGMI_SELF=0: copy the rank's own segments into its arena like the
   // peers' (the put kernel's self-copy; A/B)
   static bool self_bypass() {
-    static const bool on = [] {
-      const char* e = std::getenv("SS_XGMI_SELF");
-      return !(e && e[0] == '0');
-    }();
+    static const bool on = env_flag("SS_XGMI_SELF", true);
     return on;
   }
   // response rows of this round's received keys (per received position)
@@ -524,14 +518,11 @@ class RoundEngine {
     // sends
     const SelfSeg sv = vals_self(slot);
     if (fill) {
-      SrvSlot& S = srv_[slot];
-      const int Ps = Pd_ * sub_;
+      const BucketView bv = srv_[slot].view(Pd_ * sub_);
       if (dim_ == 1)
-        launch_bd_fill_occ_p(Ps, S.bstart, S.ubase, S.unum, S.luid, Pt<const float>(svals_),
-                             Pt<float>(rvals_), S.pj, St(stream), sv);
+        launch_bd_fill_occ(bv, Pt<const float>(svals_), Pt<float>(rvals_), 0, St(stream), sv);
       else
-        launch_srv_fill_rows(Ps, S.bstart, S.ubase, S.pj, S.luid, Pt<const float>(svals_),
-                             Pt<float>(rvals_), dim_, St(stream), sv);
+        launch_srv_fill_rows(bv, Pt<const float>(svals_), Pt<float>(rvals_), dim_, St(stream), sv);
     }
     std::vector<std::vector<long long>> parts;
     parts.push_back(part(rvals_, rc, 0, 4ll * dim_, vals_[slot], cap_,
@@ -567,17 +558,11 @@ class RoundEngine {
   std::vector<char> srv_s32_;         // per slot: the server pull stored 4-byte slots
   std::vector<char> srv_claim_;       // per slot: ... and claimed its inserts (no CAS)
   static bool srv_fill_fused() {  // SS_SRV_FILL_FUSED=0: a separate server fill kernel
-    static const bool on = [] {
-      const char* e = std::getenv("SS_SRV_FILL_FUSED");
-      return !(e && e[0] == '0');
-    }();
+    static const bool on = env_flag("SS_SRV_FILL_FUSED", true);
     return on;
   }
   static bool slot32_on() {           // SS_SLOT32=0: 8-byte slot indices
-    static const bool on = [] {
-      const char* e = std::getenv("SS_SLOT32");
-      return !(e && e[0] == '0');
-    }();
+    static const bool on = env_flag("SS_SLOT32", true);
     return on;
   }
   int nranks_ = 1, rank_ = 0, Pd_ = 1, sub_ = 1, dim_ = 1, bpp_ = 128;

@@ -449,10 +449,7 @@ static int srv_share(int P) {
 
 int srv_sub_buckets(int nsrc, long long lay_n, int ndest) {
   // SS_SRV_SUB=m: a fixed count (A/B)
-  static const int fixed = [] {
-    const char* e = std::getenv("SS_SRV_SUB");
-    return e ? std::atoi(e) : 0;
-  }();
+  static const int fixed = env_int("SS_SRV_SUB", 0);
   if (fixed > 0) return fixed > 64 ? 64 : fixed;
   // one source: its bucket's unique keys passed the worker dedup's own
   // 4096-slot table, so they fit a server table as they are
@@ -475,8 +472,7 @@ int srv_sub_buckets(int nsrc, long long lay_n, int ndest) {
 
 void launch_srv_dedup(const uint64_t* rkeys, const uint32_t* rbase, const uint32_t* rnum,
                       long long cap, int nsrc, int Pd, int m, int me, uint32_t* cnt,
-                      uint32_t* bstart, uint32_t* pj, uint32_t* luid, uint64_t* bkeys,
-                      uint32_t* ubase, uint32_t* unum, unsigned long long* ucount, uint32_t* err,
+                      const BucketViewOut& v, unsigned long long* ucount, uint32_t* err,
                       hipStream_t st, const uint32_t* roff, SelfSeg self) {
   if (nsrc < 1 || nsrc > kSrvMaxSrc || Pd < 1 || m < 1 || m > 64) throw_error("srv_dedup: bad layout");
   if (m > 1 && !roff) throw_error("srv_dedup: sub-buckets need the senders' offsets (msub)");
@@ -485,35 +481,33 @@ void launch_srv_dedup(const uint64_t* rkeys, const uint32_t* rbase, const uint32
   // cnt has P + 1 words: the last is the count kernel's arrival counter
   // (zeroed once at allocation, reset by the kernel)
   hipLaunchKernelGGL(k_srv_count, dim3((Pd + kSrvCntK - 1) / kSrvCntK), dim3(256), 0, st, R, cnt,
-                     bstart, ucount, cnt + P);
+                     v.bstart, ucount, cnt + P);
   check_launch("k_srv_count");
-  hipLaunchKernelGGL(k_srv_dedup, dim3(P), dim3(kSrvDT), 0, st, R, bstart, pj, luid, bkeys,
-                     ubase, unum, ucount, err);
+  hipLaunchKernelGGL(k_srv_dedup, dim3(P), dim3(kSrvDT), 0, st, R, v.bstart, v.pj, v.luid, v.bkeys,
+                     v.ubase, v.unum, ucount, err);
   check_launch("k_srv_dedup");
 }
 
-void launch_srv_fill_rows(int P, const uint32_t* bstart, const uint32_t* ubase,
-                          const uint32_t* pj, const uint32_t* luid, const float* rows, float* out,
-                          int D, hipStream_t st, SelfSeg self) {
-  if (P <= 0) return;
-  hipLaunchKernelGGL(k_srv_fill_rows, dim3(P, srv_share(P)), dim3(256), 0, st, bstart, ubase, pj,
-                     luid, rows, out, D, self);
+void launch_srv_fill_rows(const BucketView& v, const float* rows, float* out, int D,
+                          hipStream_t st, SelfSeg self) {
+  if (v.P <= 0) return;
+  hipLaunchKernelGGL(k_srv_fill_rows, dim3(v.P, srv_share(v.P)), dim3(256), 0, st, v.bstart,
+                     v.ubase, v.pj, v.luid, rows, out, D, self);
   check_launch("k_srv_fill_rows");
 }
 
-void launch_srv_merge_rows(int P, const uint32_t* bstart, const uint32_t* ubase,
-                           const uint32_t* unum, const uint32_t* pj, const uint32_t* luid,
-                           const float* grads, float* merged, int D, hipStream_t st,
-                           const DevTable* t, const long long* slots, const OptParams* op,
-                           SelfSeg self) {
-  if (P <= 0) return;
-  if (slots && (!t || !op || (int)t->dim != D ||
-                (int)t->width != D * (1 + opt_state_per_coord(op->kind))))
+void launch_srv_merge_rows(const BucketView& v, const float* grads, float* merged, int D,
+                           hipStream_t st, const FusedApply& fa, SelfSeg self) {
+  if (v.P <= 0) return;
+  const DevTable* t = fa.t;
+  const OptParams* op = fa.op;
+  if (fa.slots && (!t || !op || (int)t->dim != D ||
+                   (int)t->width != D * (1 + opt_state_per_coord(op->kind))))
     throw_error("srv_merge_rows: a fused update needs the table of these rows");
-  if (!slots && !merged) throw_error("srv_merge_rows: merged rows or a fused update");
-  hipLaunchKernelGGL(k_srv_merge_rows, dim3(P, srv_share(P)), dim3(512), 0, st, bstart, ubase,
-                     unum, pj, luid,
-                     grads, merged, D, t ? *t : DevTable{}, slots, op ? *op : OptParams{}, self);
+  if (!fa.slots && !merged) throw_error("srv_merge_rows: merged rows or a fused update");
+  hipLaunchKernelGGL(k_srv_merge_rows, dim3(v.P, srv_share(v.P)), dim3(512), 0, st, v.bstart,
+                     v.ubase, v.unum, v.pj, v.luid, grads, merged, D, t ? *t : DevTable{},
+                     fa.slots, op ? *op : OptParams{}, self);
   check_launch("k_srv_merge_rows");
 }
 

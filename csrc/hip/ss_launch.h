@@ -4,8 +4,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "bdindex.h"
 #include "ss_device.h"
@@ -20,6 +22,71 @@ inline void check_hip(hipError_t e, const char* what) {
 
 inline void check_launch(const char* what) { check_hip(hipGetLastError(), what); }
 
+// Run-time value -> compile-time constant: calls f(std::integral_constant<int,
+// V>{}) for the V of the list that equals v, so f's body names the kernels
+// instantiated for exactly that list.  Any other v throws the caller's message
+// (with_value) or takes the list's first value (with_value_or).
+template <int... Vs, class F>
+void with_value(int v, const char* err, F&& f) {
+  if (!((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...)) throw_error(err);
+}
+template <int Default, int... Vs, class F>
+void with_value_or(int v, F&& f) {
+  if (!((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...))
+    f(std::integral_constant<int, Default>{});
+}
+
+// Environment knobs (utils/knobs.py lists them by the file that names them):
+// on unless the value starts with '0' / off unless it is set and does not;
+// an integer, `def` when unset.  The readers cache the result in a static.
+inline bool env_flag(const char* name, bool def) {
+  const char* e = std::getenv(name);
+  return e ? e[0] != '0' : def;
+}
+inline int env_int(const char* name, int def) {
+  const char* e = std::getenv(name);
+  return e ? std::atoi(e) : def;
+}
+
+// The fused update of a merge kernel: the table, the rule, the unique keys'
+// slots — 8-byte indices (slots) or 4-byte ones (slots32), at most one of
+// them — the pull's (w, h) snapshot and, for whole [row | key] slot stores,
+// the buckets' staged keys.  All null: the merge only writes gradients.
+struct FusedApply {
+  const DevTable* t = nullptr;
+  const OptParams* op = nullptr;
+  const long long* slots = nullptr;
+  const int* slots32 = nullptr;
+  const float* snap = nullptr;
+  const uint64_t* bkeys = nullptr;
+  bool on() const { return slots || slots32; }
+  DevTable table() const { return on() ? *t : DevTable{}; }
+  OptParams rule() const { return on() ? *op : OptParams{}; }
+};
+// ... from a slot buffer that holds 4-byte indices when `slot32` (what a
+// 4-byte-slot pull left there), else 8-byte ones
+inline FusedApply fused_apply(const DevTable* t, const OptParams* op, const void* slots,
+                              bool slot32, const float* snap, const uint64_t* bkeys = nullptr) {
+  return {t, op, slot32 ? nullptr : static_cast<const long long*>(slots),
+          slot32 ? static_cast<const int*>(slots) : nullptr, snap, bkeys};
+}
+// refuses (texts prefixed `who`) a fused update that is not of scalar two-float
+// rows under AdaGrad or FTRL (z, n), or key stores without a snapshot merge
+// into 16-byte slots; compact_ids: the form has an occurrence-segment index
+// `osi`, which a fused update needs 0 (bdedup.hip)
+void check_fused_scalar(const char* who, const FusedApply& f, bool compact_ids, int osi = 0);
+
+// A step's loss accumulator handed off by a kernel that runs anyway: acc[0..n)
+// moves to out and is left zero.  acc null: no hand-off.
+struct LossHandoff {
+  float* acc = nullptr;
+  float* out = nullptr;
+  int n = 0;
+  void check(const char* msg) const {
+    if (acc && (!out || n <= 0)) throw_error(msg);
+  }
+};
+
 // --- table.hip
 void launch_probe(const DevTable& t, const uint64_t* keys, const SegList& sl, long long max_n,
                   long long* slots, const InitParams& ip, int insert,
@@ -29,28 +96,23 @@ void launch_gather(const DevTable& t, const long long* slots, const SegList& sl,
 void launch_pull_unique(const DevTable& t, const uint64_t* keys, const SegList& sl,
                         long long max_n, long long* slots, float* out, const InitParams& ip,
                         unsigned long long* size_ctr, int* err, int G, hipStream_t st);
-void launch_pull_unique_bk(const DevTable& t, const uint64_t* bkeys, const uint32_t* bstart,
-                           const uint32_t* unum, const uint32_t* ubase, int P, long long* slots,
-                           float* out, const InitParams& ip, unsigned long long* size_ctr,
-                           int* err, int G, hipStream_t st, float* snap = nullptr,
-                           int slot32 = 0);
+void launch_pull_unique_bk(const DevTable& t, const BucketView& v, long long* slots, float* out,
+                           const InitParams& ip, unsigned long long* size_ctr, int* err, int G,
+                           hipStream_t st, float* snap = nullptr, int slot32 = 0);
 // region tables, region-aligned buckets (launch_bd_dedup returned rbits):
 // one workgroup per bucket claims new keys' slots in LDS (no device atomic,
 // nothing written to the table); the fused merge stores [w | h | key]
-// (launch_bd_reduce with bkeys) or launch_commit_claims writes them
-void launch_pull_claim_bk(const DevTable& t, const uint64_t* bkeys, const uint32_t* bstart,
-                          const uint32_t* unum, const uint32_t* ubase, int P, int* slots32,
-                          float* out, float* snap, const InitParams& ip,
-                          unsigned long long* size_ctr, int* err, hipStream_t st,
-                          const uint32_t* luid = nullptr, float* occ = nullptr,
-                          const uint32_t* pj = nullptr, SelfSeg self = SelfSeg{});
+// (launch_bd_reduce with bkeys) or launch_commit_claims writes them.
+// occ (with v.luid): the rows per occurrence too, at the occurrence's
+// position, or — v.pj set, a server's response fill — at pj[position]
+void launch_pull_claim_bk(const DevTable& t, const BucketView& v, int* slots32, float* out,
+                          float* snap, const InitParams& ip, unsigned long long* size_ctr,
+                          int* err, hipStream_t st, float* occ = nullptr,
+                          SelfSeg self = SelfSeg{});
 // read-only lookup of a bucket view's unique keys (no insert; zeros if absent)
-void launch_lookup_bk(const DevTable& t, const uint64_t* bkeys, const uint32_t* bstart,
-                      const uint32_t* unum, const uint32_t* ubase, int P, float* out, int G,
-                      hipStream_t st);
+void launch_lookup_bk(const DevTable& t, const BucketView& v, float* out, int G, hipStream_t st);
 bool apply_masked_ok(const DevTable& t, const OptParams& op);
-void launch_commit_claims(const DevTable& t, const uint64_t* bkeys, const uint32_t* bstart,
-                          const uint32_t* unum, const uint32_t* ubase, int P, const int* slots32,
+void launch_commit_claims(const DevTable& t, const BucketView& v, const int* slots32,
                           const float* snap, hipStream_t st, int* err = nullptr);
 // only (optional): apply only at positions with only[pos] != 0 (wide rows);
 // slot32: `slots` holds 4-byte slot indices (a snapshot pull of scalar rows)
@@ -131,9 +193,8 @@ void launch_w2v_cbow(const uint32_t* inv_c, const uint32_t* inv_w, const uint32_
                      hipStream_t st, float* ograd = nullptr, float* otail = nullptr);
 // flips the namespace bit (1 << 40) of the first n keys of a window-layout batch
 void launch_w2v_cbow_keys(uint64_t* keys, long long n, hipStream_t st);
-void launch_w2v_osort(int P, const uint32_t* bstart, const uint32_t* unum, const uint32_t* ubase,
-                      const uint32_t* pj, const uint32_t* luid, uint32_t* ord, uint32_t* items,
-                      hipStream_t st, uint8_t* uhot = nullptr);
+void launch_w2v_osort(const BucketView& v, uint32_t* ord, uint32_t* items, hipStream_t st,
+                      uint8_t* uhot = nullptr);
 void launch_w2v_pp(const uint32_t* inv_c, const uint32_t* inv_w, const uint32_t* inv_n,
                    const int32_t* meta, int B, int W, int K, int D, const float* uvals,
                    float* ograd, float* gpair, float* loss_sum, float* pair_sum, hipStream_t st,
@@ -141,9 +202,8 @@ void launch_w2v_pp(const uint32_t* inv_c, const uint32_t* inv_w, const uint32_t*
 void launch_w2v_oreduce(const uint32_t* items, long long n, const uint32_t* ord, const float* ograd,
                         const float* otail, int B, int W, int D, float* ugrad, hipStream_t st,
                         const float* gnc = nullptr, long long negbase = 0,
-                        const float* uvals = nullptr, float* acc = nullptr,
-                        float* acc_out = nullptr, int acc_n = 0, const DevTable* tab = nullptr,
-                        const long long* slots = nullptr, const OptParams* op = nullptr);
+                        const float* uvals = nullptr, const LossHandoff& loss = {},
+                        const FusedApply& fa = {});
 void launch_w2v_stream_gen(uint64_t seed, long long base, int B, int W, int L, long long nneg,
                            long long V, float noise, uint64_t* keys, int32_t* meta,
                            hipStream_t st, const long long* step_dev, long long step_mul,
@@ -210,54 +270,43 @@ int bd_target_dist();
 int bd_target_for(int nranks, bool records);
 void launch_rec_grad(const unsigned long long* ucount, int nd, long long gap, const uint32_t* spj,
                      const float* gs, const float* xval, int F, float* grec, hipStream_t st,
-                     float* lacc = nullptr, float* lacc_out = nullptr, int lacc_n = 0,
-                     int skip = -1);
-void launch_bd_reduce(long long n, int nranks, const uint32_t* scratch, const uint32_t* pj,
-                      const uint32_t* luid, const float* gs, const float* xval, int F,
+                     const LossHandoff& loss = {}, int skip = -1);
+// the view of the BdLayout scratch a dedup of n keys wrote (one bd_layout);
+// n <= 0: an empty view (P = 0), which every bucket launcher returns on
+BucketView bd_view(long long n, int nranks, int ndest, const uint32_t* scratch,
+                   const uint32_t* pj, const uint32_t* luid, const uint64_t* bkeys = nullptr);
+// merged gradients per distinct key (scalar rows), with `fa` the update fused.
+// srv: a server merge's own view (server.hip) instead of a worker dedup's —
+// no occurrence segments, own rows read in place (self); its refusals are
+// prefixed bd_reduce_p
+void launch_bd_reduce(const BucketView& v, const float* gs, const float* xval, int F,
                       float* ugrad, hipStream_t st, int osi = 0,
-                      const uint8_t* usingle = nullptr, const DevTable* t = nullptr,
-                      const long long* slots = nullptr, const float* snap = nullptr,
-                      const OptParams* op = nullptr, int ndest = 0, int slot32 = 0,
-                      float* lacc = nullptr, float* lacc_out = nullptr, int lacc_n = 0,
-                      const uint64_t* bkeys = nullptr);
+                      const uint8_t* usingle = nullptr, const FusedApply& fa = {},
+                      const LossHandoff& loss = {}, SelfSeg self = {}, bool srv = false);
 // occ[p] = uvals[uid of occurrence position p] (scalar rows; 0 where none):
 // one workgroup per dedup bucket, for the LR forward's one-gather mode
-void launch_bd_fill_occ(long long n, int nranks, const uint32_t* scratch, const uint32_t* luid,
-                        const float* uvals, float* occ, int osi, hipStream_t st, int ndest, const uint32_t* pj = nullptr);
-void launch_bd_unplace(long long n, int nranks, const uint32_t* scratch, const float* src,
-                       float* dst, int dim, hipStream_t st, int ndest = 0);
+// (v.pj set: occ[pj[p]], a server's response fill)
+void launch_bd_fill_occ(const BucketView& v, const float* uvals, float* occ, int osi,
+                        hipStream_t st, SelfSeg self = {});
+void launch_bd_unplace(const BucketView& v, const float* src, float* dst, int dim,
+                       hipStream_t st);
 
-void launch_bd_reduce_fm(long long n, int nranks, const uint32_t* scratch, const uint32_t* pj,
-                         const uint32_t* luid, const float* gs, const float* gss, int F, int dim,
-                         const float* uvals, float* ugrad, hipStream_t st,
-                         uint32_t* ovf = nullptr, int ndest = 0);
+// n: the call's keys (sizes the overflow list)
+void launch_bd_reduce_fm(const BucketView& v, long long n, const float* gs, const float* gss,
+                         int F, int dim, const float* uvals, float* ugrad, hipStream_t st,
+                         uint32_t* ovf = nullptr);
 long long bd_fm_ovf_words(long long n);
-
-// explicit-layout forms of the bucket kernels (server-side merge)
-void launch_bd_reduce_p(int P, const uint32_t* bstart, const uint32_t* ubase, const uint32_t* unum,
-                        const uint32_t* pj, const uint32_t* luid, const float* gs, int F,
-                        float* ugrad, const DevTable* t, const long long* slots,
-                        const float* snap, const OptParams* op, hipStream_t st,
-                        SelfSeg self = {}, int slot32 = 0, const uint64_t* bkeys = nullptr);
-void launch_bd_fill_occ_p(int P, const uint32_t* bstart, const uint32_t* ubase,
-                          const uint32_t* unum, const uint32_t* luid, const float* uvals,
-                          float* occ, const uint32_t* pj, hipStream_t st, SelfSeg self = {});
 
 // --- server.hip (N>1: merge of the keys a round receives from all sources)
 int srv_sub_buckets(int nsrc, long long lay_n = 0, int ndest = 0);
 void launch_srv_dedup(const uint64_t* rkeys, const uint32_t* rbase, const uint32_t* rnum,
                       long long cap, int nsrc, int Pd, int m, int me, uint32_t* cnt,
-                      uint32_t* bstart, uint32_t* pj, uint32_t* luid, uint64_t* bkeys,
-                      uint32_t* ubase, uint32_t* unum, unsigned long long* ucount, uint32_t* err,
+                      const BucketViewOut& v, unsigned long long* ucount, uint32_t* err,
                       hipStream_t st, const uint32_t* roff = nullptr, SelfSeg self = {});
-void launch_srv_fill_rows(int P, const uint32_t* bstart, const uint32_t* ubase,
-                          const uint32_t* pj, const uint32_t* luid, const float* rows, float* out,
-                          int D, hipStream_t st, SelfSeg self = {});
-void launch_srv_merge_rows(int P, const uint32_t* bstart, const uint32_t* ubase,
-                           const uint32_t* unum, const uint32_t* pj, const uint32_t* luid,
-                           const float* grads, float* merged, int D, hipStream_t st,
-                           const DevTable* t = nullptr, const long long* slots = nullptr,
-                           const OptParams* op = nullptr, SelfSeg self = {});
+void launch_srv_fill_rows(const BucketView& v, const float* rows, float* out, int D,
+                          hipStream_t st, SelfSeg self = {});
+void launch_srv_merge_rows(const BucketView& v, const float* grads, float* merged, int D,
+                           hipStream_t st, const FusedApply& fa = {}, SelfSeg self = {});
 
 // --- w2v.hip
 size_t w2v_smem_bytes(int D);

@@ -968,21 +968,20 @@ static inline int grid_for(long long groups, int G, int cap_blocks = 16384) {
   return (int)b;
 }
 
-#define SS_DISPATCH_G(G, ...)                   \
-  switch (G) {                                  \
-    case 1: { constexpr int kG = 1; __VA_ARGS__; } break;   \
-    case 4: { constexpr int kG = 4; __VA_ARGS__; } break;   \
-    case 16: { constexpr int kG = 16; __VA_ARGS__; } break; \
-    case 64: { constexpr int kG = 64; __VA_ARGS__; } break; \
-    default: throw_error("unsupported lane-group size");    \
-  }
+// f(kG) for the lane-group size G the kernels are instantiated for
+template <class F>
+static void with_lane_group(int G, F&& f) {
+  with_value<1, 4, 16, 64>(G, "unsupported lane-group size", f);
+}
+// f(dim) for a wide row's 32 / 64 / 128 coordinates (wide_rows holds)
+template <class F>
+static void with_wide_dim(int dim, F&& f) {
+  with_value_or<128, 32, 64>(dim, f);
+}
 
 // the 8-lane / 16-byte forms for wide fp32 rows (SS_PULL_VEC=0: the lane-group forms)
 static bool pull_vec_on() {
-  static const bool on = [] {
-    const char* e = std::getenv("SS_PULL_VEC");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_flag("SS_PULL_VEC", true);
   return on;
 }
 // wide rows (word2vec): fp32 rows 16-byte aligned, or compact bf16 rows
@@ -1002,16 +1001,22 @@ void launch_probe(const DevTable& t, const uint64_t* keys, const SegList& sl, lo
                   long long* slots, const InitParams& ip, int insert,
                   unsigned long long* size_ctr, int* err, int G, hipStream_t st) {
   if (max_n <= 0) return;
-  SS_DISPATCH_G(G, hipLaunchKernelGGL(k_probe<kG>, dim3(grid_for(max_n, kG)), dim3(256), 0, st, t,
-                                      keys, sl, slots, ip, insert, size_ctr, err));
+  with_lane_group(G, [&](auto g) {
+    constexpr int kG = g.value;
+    hipLaunchKernelGGL(k_probe<kG>, dim3(grid_for(max_n, kG)), dim3(256), 0, st, t, keys, sl,
+                       slots, ip, insert, size_ctr, err);
+  });
   check_launch("k_probe");
 }
 
 void launch_gather(const DevTable& t, const long long* slots, const SegList& sl, long long max_n,
                    float* out, int G, hipStream_t st) {
   if (max_n <= 0) return;
-  SS_DISPATCH_G(G, hipLaunchKernelGGL(k_gather<kG>, dim3(grid_for(max_n, kG)), dim3(256), 0, st,
-                                      t, slots, sl, out));
+  with_lane_group(G, [&](auto g) {
+    constexpr int kG = g.value;
+    hipLaunchKernelGGL(k_gather<kG>, dim3(grid_for(max_n, kG)), dim3(256), 0, st, t, slots, sl,
+                       out);
+  });
   check_launch("k_gather");
 }
 
@@ -1024,17 +1029,18 @@ void launch_pull_unique(const DevTable& t, const uint64_t* keys, const SegList& 
   // (count / scatter: few, large workgroups) is not starved beside it (see
   // launch_bd_dedup)
   static const int pull_cap = grid_cap_per_cu(4);
-  SS_DISPATCH_G(G, hipLaunchKernelGGL(k_pull_unique<kG>, dim3(grid_for(max_n, kG, pull_cap)),
-                                      dim3(256), 0, st, t, keys, sl, slots, out, ip, size_ctr,
-                                      err));
+  with_lane_group(G, [&](auto g) {
+    constexpr int kG = g.value;
+    hipLaunchKernelGGL(k_pull_unique<kG>, dim3(grid_for(max_n, kG, pull_cap)), dim3(256), 0, st,
+                       t, keys, sl, slots, out, ip, size_ctr, err);
+  });
   check_launch("k_pull_unique");
 }
 
-void launch_pull_unique_bk(const DevTable& t, const uint64_t* bkeys, const uint32_t* bstart,
-                           const uint32_t* unum, const uint32_t* ubase, int P, long long* slots,
-                           float* out, const InitParams& ip, unsigned long long* size_ctr,
-                           int* err, int G, hipStream_t st, float* snap, int slot32) {
-  if (P <= 0) return;
+void launch_pull_unique_bk(const DevTable& t, const BucketView& v, long long* slots, float* out,
+                           const InitParams& ip, unsigned long long* size_ctr, int* err, int G,
+                           hipStream_t st, float* snap, int slot32) {
+  if (v.P <= 0) return;
   if (snap && (t.bf16 || !(G == 1 && t.dim == 1 && t.width == 2 && t.row_off % 8 == 0 &&
                            t.stride % 8 == 0)))
     throw std::invalid_argument("pull snapshot: scalar (w, h) rows with G = 1 only");
@@ -1049,23 +1055,22 @@ void launch_pull_unique_bk(const DevTable& t, const uint64_t* bkeys, const uint3
   const int ny = G == 1 ? 4 : 2;
   // wide fp32 rows: 8 lanes per key, 16-byte row accesses (k_pull_rows_bk)
   if (!snap && pull_vec_on() && wide_rows(t) && reinterpret_cast<uintptr_t>(out) % 16 == 0) {
-#define SS_PRB(DD, B)                                                                          \
-  hipLaunchKernelGGL((k_pull_rows_bk<DD, B>), dim3(P, ny), dim3(256), 0, st, t, bkeys, bstart,   \
-                     unum, ubase, slots, out, ip, size_ctr, err)
-    switch (t.dim) {
-      case 32: if (t.bf16) SS_PRB(32, true); else SS_PRB(32, false); break;
-      case 64: if (t.bf16) SS_PRB(64, true); else SS_PRB(64, false); break;
-      default: if (t.bf16) SS_PRB(128, true); else SS_PRB(128, false); break;
-    }
-#undef SS_PRB
+    with_wide_dim(t.dim, [&](auto d) {
+      if (t.bf16)
+        hipLaunchKernelGGL((k_pull_rows_bk<d.value, true>), dim3(v.P, ny), dim3(256), 0, st, t,
+                           v.bkeys, v.bstart, v.unum, v.ubase, slots, out, ip, size_ctr, err);
+      else
+        hipLaunchKernelGGL((k_pull_rows_bk<d.value, false>), dim3(v.P, ny), dim3(256), 0, st, t,
+                           v.bkeys, v.bstart, v.unum, v.ubase, slots, out, ip, size_ctr, err);
+    });
     check_launch("k_pull_rows_bk");
     return;
   }
   // narrow fp32 rows with key + parameters in the slot's first 64 bytes (FM)
   if (!snap && pull_vec_on() && !t.bf16 && t.key_off == 0 && t.row_off == 8 &&
       t.stride % 16 == 0 && t.stride >= 64 && t.dim >= 2 && 8 + 4 * t.dim <= 64) {
-    hipLaunchKernelGGL(k_pull_narrow_bk, dim3(P, ny), dim3(256), 0, st, t, bkeys, bstart, unum,
-                       ubase, slots, out, ip, size_ctr, err);
+    hipLaunchKernelGGL(k_pull_narrow_bk, dim3(v.P, ny), dim3(256), 0, st, t, v.bkeys, v.bstart,
+                       v.unum, v.ubase, slots, out, ip, size_ctr, err);
     check_launch("k_pull_narrow_bk");
     return;
   }
@@ -1077,18 +1082,20 @@ void launch_pull_unique_bk(const DevTable& t, const uint64_t* bkeys, const uint3
       throw std::invalid_argument("pull: 4-byte slots need snapshot 16-byte slots, cap < 2^31");
     one16 = 2;
   }
-  SS_DISPATCH_G(G, hipLaunchKernelGGL(k_pull_unique_bk<kG>, dim3(P, ny), dim3(256), 0, st, t,
-                                      bkeys, bstart, unum, ubase, slots, out, ip, size_ctr, err,
-                                      reinterpret_cast<float2*>(snap), one16));
+  with_lane_group(G, [&](auto g) {
+    hipLaunchKernelGGL(k_pull_unique_bk<g.value>, dim3(v.P, ny), dim3(256), 0, st, t, v.bkeys,
+                       v.bstart, v.unum, v.ubase, slots, out, ip, size_ctr, err,
+                       reinterpret_cast<float2*>(snap), one16);
+  });
   check_launch("k_pull_unique_bk");
 }
 
-void launch_lookup_bk(const DevTable& t, const uint64_t* bkeys, const uint32_t* bstart,
-                      const uint32_t* unum, const uint32_t* ubase, int P, float* out, int G,
-                      hipStream_t st) {
-  if (P <= 0) return;
-  SS_DISPATCH_G(G, hipLaunchKernelGGL(k_lookup_bk<kG>, dim3(P, 2), dim3(256), 0, st, t, bkeys,
-                                      bstart, unum, ubase, out));
+void launch_lookup_bk(const DevTable& t, const BucketView& v, float* out, int G, hipStream_t st) {
+  if (v.P <= 0) return;
+  with_lane_group(G, [&](auto g) {
+    hipLaunchKernelGGL(k_lookup_bk<g.value>, dim3(v.P, 2), dim3(256), 0, st, t, v.bkeys, v.bstart,
+                       v.unum, v.ubase, out);
+  });
   check_launch("k_lookup_bk");
 }
 
@@ -1099,50 +1106,39 @@ static void check_claim_table(const DevTable& t) {
         "claimed pulls: a region table of 16-byte [w|h|key] slots under 2^31 slots");
 }
 
-void launch_pull_claim_bk(const DevTable& t, const uint64_t* bkeys, const uint32_t* bstart,
-                          const uint32_t* unum, const uint32_t* ubase, int P, int* slots32,
-                          float* out, float* snap, const InitParams& ip,
-                          unsigned long long* size_ctr, int* err, hipStream_t st,
-                          const uint32_t* luid, float* occ, const uint32_t* pj,
-                          SelfSeg self) {
-  if (P <= 0) return;
+void launch_pull_claim_bk(const DevTable& t, const BucketView& v, int* slots32, float* out,
+                          float* snap, const InitParams& ip, unsigned long long* size_ctr,
+                          int* err, hipStream_t st, float* occ, SelfSeg self) {
+  if (v.P <= 0) return;
   check_claim_table(t);
-  if (!slots32 || !(out || occ) || !snap || (occ && !luid))
+  if (!slots32 || !(out || occ) || !snap || (occ && !v.luid))
     throw std::invalid_argument("claimed pull: slots, rows (or occurrence rows + luid), snapshot");
   // workgroup size (SS_CLAIM_T: 256 / 512 / 1024): one workgroup per bucket
   static const int ct = [] {
-    const char* e = std::getenv("SS_CLAIM_T");
-    const int v = e ? std::atoi(e) : kClaimT;
-    return (v == 64 || v == 128 || v == 512 || v == 1024) ? v : 256;
+    const int x = env_int("SS_CLAIM_T", kClaimT);
+    return (x == 64 || x == 128 || x == 512 || x == 1024) ? x : 256;
   }();
-#define SS_CLAIM_LAUNCH(CT)                                                                     \
-  hipLaunchKernelGGL((k_pull_claim_bk<CT>), dim3(P), dim3(CT), 0, st, t, bkeys, bstart, unum,    \
-                     ubase, slots32, out, reinterpret_cast<float2*>(snap), ip, size_ctr, err, luid, \
-                     occ, pj, self)
-  static const int cts = [] {
-    const char* e = std::getenv("SS_CLAIM_TS");
-    return e && std::atoi(e) == 4096 ? 4096 : kClaimTS;
-  }();
+  static const int cts = env_int("SS_CLAIM_TS", kClaimTS) == 4096 ? 4096 : kClaimTS;
+  float2* sn = reinterpret_cast<float2*>(snap);
   if (ct == 256 && cts == 4096)
-    hipLaunchKernelGGL((k_pull_claim_bk<256, 4096>), dim3(P), dim3(256), 0, st, t, bkeys, bstart,
-                       unum, ubase, slots32, out, reinterpret_cast<float2*>(snap), ip, size_ctr,
-                       err, luid, occ, pj, self);
-  else if (ct == 256) SS_CLAIM_LAUNCH(256);
-  else if (ct == 64) SS_CLAIM_LAUNCH(64);
-  else if (ct == 128) SS_CLAIM_LAUNCH(128);
-  else if (ct == 512) SS_CLAIM_LAUNCH(512);
-  else SS_CLAIM_LAUNCH(1024);
-#undef SS_CLAIM_LAUNCH
+    hipLaunchKernelGGL((k_pull_claim_bk<256, 4096>), dim3(v.P), dim3(256), 0, st, t, v.bkeys,
+                       v.bstart, v.unum, v.ubase, slots32, out, sn, ip, size_ctr, err, v.luid,
+                       occ, v.pj, self);
+  else
+    with_value_or<1024, 256, 64, 128, 512>(ct, [&](auto c) {
+      hipLaunchKernelGGL((k_pull_claim_bk<c.value>), dim3(v.P), dim3(c.value), 0, st, t, v.bkeys,
+                         v.bstart, v.unum, v.ubase, slots32, out, sn, ip, size_ctr, err, v.luid,
+                         occ, v.pj, self);
+    });
   check_launch("k_pull_claim_bk");
 }
 
-void launch_commit_claims(const DevTable& t, const uint64_t* bkeys, const uint32_t* bstart,
-                          const uint32_t* unum, const uint32_t* ubase, int P, const int* slots32,
+void launch_commit_claims(const DevTable& t, const BucketView& v, const int* slots32,
                           const float* snap, hipStream_t st, int* err) {
-  if (P <= 0) return;
+  if (v.P <= 0) return;
   check_claim_table(t);
-  hipLaunchKernelGGL(k_commit_claims, dim3(P), dim3(256), 0, st, t, bkeys, bstart, unum, ubase,
-                     slots32, reinterpret_cast<const float2*>(snap), err);
+  hipLaunchKernelGGL(k_commit_claims, dim3(v.P), dim3(256), 0, st, t, v.bkeys, v.bstart, v.unum,
+                     v.ubase, slots32, reinterpret_cast<const float2*>(snap), err);
   check_launch("k_commit_claims");
 }
 
@@ -1162,15 +1158,14 @@ void launch_apply(const DevTable& t, const long long* slots, const float* grads,
   if (!snap && pull_vec_on() && wide_rows(t) && W == t.width &&
       reinterpret_cast<uintptr_t>(grads) % 16 == 0) {
     const long long grid = grid_for(max_n, kPvL, 1 << 22);
-#define SS_ARB(DD, B)                                                                          \
-  hipLaunchKernelGGL((k_apply_rows<DD, B>), dim3(grid), dim3(256), 0, st, t, slots, grads, sl,   \
-                     op, only)
-    switch (t.dim) {
-      case 32: if (t.bf16) SS_ARB(32, true); else SS_ARB(32, false); break;
-      case 64: if (t.bf16) SS_ARB(64, true); else SS_ARB(64, false); break;
-      default: if (t.bf16) SS_ARB(128, true); else SS_ARB(128, false); break;
-    }
-#undef SS_ARB
+    with_wide_dim(t.dim, [&](auto d) {
+      if (t.bf16)
+        hipLaunchKernelGGL((k_apply_rows<d.value, true>), dim3(grid), dim3(256), 0, st, t, slots,
+                           grads, sl, op, only);
+      else
+        hipLaunchKernelGGL((k_apply_rows<d.value, false>), dim3(grid), dim3(256), 0, st, t, slots,
+                           grads, sl, op, only);
+    });
     check_launch("k_apply_rows");
     return;
   }
@@ -1179,22 +1174,30 @@ void launch_apply(const DevTable& t, const long long* slots, const float* grads,
                 "or bf16 rows, SS_PULL_VEC=1)");
   if (!snap && !t.bf16 && G > 1 && G <= 16 && t.dim > 1 && W <= (uint32_t)kStageMaxW &&
       W % 2 == 0 && W == t.width && t.row_off % 8 == 0 && t.stride % 8 == 0) {
-    SS_DISPATCH_G(G, hipLaunchKernelGGL(k_apply_st<kG>, dim3(grid_for(max_n, kG, 1 << 22)),
-                                        dim3(256), 0, st, t, slots, grads, sl, op));
+    with_lane_group(G, [&](auto g) {
+      constexpr int kG = g.value;
+      hipLaunchKernelGGL(k_apply_st<kG>, dim3(grid_for(max_n, kG, 1 << 22)), dim3(256), 0, st, t,
+                         slots, grads, sl, op);
+    });
     check_launch("k_apply_st");
     return;
   }
-  SS_DISPATCH_G(G, hipLaunchKernelGGL(k_apply<kG>, dim3(grid_for(max_n, kG, 1 << 22)),
-                                      dim3(256), 0, st, t, slots, grads, sl, op,
-                                      reinterpret_cast<const float2*>(snap), slot32));
+  with_lane_group(G, [&](auto g) {
+    constexpr int kG = g.value;
+    hipLaunchKernelGGL(k_apply<kG>, dim3(grid_for(max_n, kG, 1 << 22)), dim3(256), 0, st, t,
+                       slots, grads, sl, op, reinterpret_cast<const float2*>(snap), slot32);
+  });
   check_launch("k_apply");
 }
 
 void launch_assign(const DevTable& t, const uint64_t* keys, const float* rows, long long n,
                    unsigned long long* size_ctr, int* err, int G, hipStream_t st) {
   if (n <= 0) return;
-  SS_DISPATCH_G(G, hipLaunchKernelGGL(k_assign<kG>, dim3(grid_for(n, kG)), dim3(256), 0, st, t,
-                                      keys, rows, n, size_ctr, err));
+  with_lane_group(G, [&](auto g) {
+    constexpr int kG = g.value;
+    hipLaunchKernelGGL(k_assign<kG>, dim3(grid_for(n, kG)), dim3(256), 0, st, t, keys, rows, n,
+                       size_ctr, err);
+  });
   check_launch("k_assign");
 }
 

@@ -1512,10 +1512,7 @@ size_t w2v_smem_bytes(int D) {
 // 0.101-0.103 ms/step at half the CUs).  SS_W2V_WIN_GRID overrides (0: one
 // workgroup per tile)
 static int w2v_tile_grid(int tiles, bool atomics) {
-  static const int env = [] {
-    const char* e = std::getenv("SS_W2V_WIN_GRID");
-    return e ? std::atoi(e) : -1;
-  }();
+  static const int env = env_int("SS_W2V_WIN_GRID", -1);
   static const int half = [] {
     int dev = 0, cus = 0;
     check_hip(hipGetDevice(&dev), "hipGetDevice");
@@ -1543,12 +1540,7 @@ static void smem_attr_once(size_t bytes) {
 // instantiated for; any other D throws the launcher's message `err`.
 template <class F>
 static void with_dim(int D, const char* err, F&& f) {
-  switch (D) {
-    case 32: f(std::integral_constant<int, 32>{}); break;
-    case 64: f(std::integral_constant<int, 64>{}); break;
-    case 128: f(std::integral_constant<int, 128>{}); break;
-    default: throw_error(err);
-  }
+  with_value<32, 64, 128>(D, err, f);
 }
 
 template <int D>
@@ -1591,12 +1583,11 @@ void launch_w2v_sgns(const uint32_t* inv_c, const uint32_t* inv_x, const uint32_
   check_launch("k_w2v_sgns");
 }
 
-void launch_w2v_osort(int P, const uint32_t* bstart, const uint32_t* unum, const uint32_t* ubase,
-                      const uint32_t* pj, const uint32_t* luid, uint32_t* ord, uint32_t* items,
-                      hipStream_t st, uint8_t* uhot) {
-  if (P <= 0) return;
-  hipLaunchKernelGGL(k_w2v_osort, dim3(P), dim3(kOsT), 0, st, bstart, unum, ubase, pj, luid, ord,
-                     reinterpret_cast<uint4*>(items), uhot);
+void launch_w2v_osort(const BucketView& v, uint32_t* ord, uint32_t* items, hipStream_t st,
+                      uint8_t* uhot) {
+  if (v.P <= 0) return;
+  hipLaunchKernelGGL(k_w2v_osort, dim3(v.P), dim3(kOsT), 0, st, v.bstart, v.unum, v.ubase, v.pj,
+                     v.luid, ord, reinterpret_cast<uint4*>(items), uhot);
   check_launch("k_w2v_osort");
 }
 
@@ -1738,49 +1729,42 @@ __global__ __launch_bounds__(256) void k_w2v_oreduce_pp2(
 }
 
 static int pp_qf() {
-  static const int v = [] {
-    const char* e = std::getenv("SS_W2V_PP_QF");
-    return e ? std::atoi(e) : 2;
-  }();
+  static const int v = env_int("SS_W2V_PP_QF", 2);
   return v;
 }
 // SS_W2V_PP_ITEMS: items per half-wave of the per-pair reduce, 1 or 2
 static int pp_items() {
-  static const int v = [] {
-    const char* e = std::getenv("SS_W2V_PP_ITEMS");
-    return e ? std::atoi(e) : 2;
-  }();
+  static const int v = env_int("SS_W2V_PP_ITEMS", 2);
   return v;
 }
 
 // SS_W2V_EARLY_SLOT=0: the fused update loads its slot index after the
 // occurrence gathers instead of beside the first (A/B)
 static int early_slot() {
-  static const int v = [] {
-    const char* e = std::getenv("SS_W2V_EARLY_SLOT");
-    return e ? std::atoi(e) : 1;
-  }();
+  static const int v = env_int("SS_W2V_EARLY_SLOT", 1);
   return v;
 }
 
 void launch_w2v_oreduce(const uint32_t* items, long long n, const uint32_t* ord, const float* ograd,
                         const float* otail, int B, int W, int D, float* ugrad, hipStream_t st,
-                        const float* gnc, long long negbase, const float* uvals, float* acc,
-                        float* acc_out, int acc_n, const DevTable* tab, const long long* slots,
-                        const OptParams* op) {
+                        const float* gnc, long long negbase, const float* uvals,
+                        const LossHandoff& loss, const FusedApply& fa) {
   if (gnc && !uvals) throw_error("w2v_oreduce: scaled negative rows need the center rows");
-  DevTable tv{};
-  OptParams opv{};
+  const DevTable* tab = fa.t;
+  const OptParams* op = fa.op;
+  const long long* slots = fa.slots;
   if (slots) {
     const int ns = op ? opt_state_per_coord(op->kind) : 0;
     const int al = tab && tab->bf16 ? 8 : 16;
     if (!tab || !op || (int)tab->dim != D || (int)tab->width != D * (1 + ns) ||
         tab->row_off % al != 0 || tab->stride % al != 0)
       throw_error("w2v_oreduce: a fused update needs aligned rows of this D");
-    tv = *tab;
-    opv = *op;
   }
-  if (acc && (!acc_out || acc_n <= 0)) throw_error("w2v_oreduce: accumulator hand-off needs acc_out");
+  const DevTable tv = fa.table();
+  const OptParams opv = fa.rule();
+  loss.check("w2v_oreduce: accumulator hand-off needs acc_out");
+  float *acc = loss.acc, *acc_out = loss.out;
+  const int acc_n = loss.n;
   if (n <= 0 && !acc) return;
   if (W < 1 || W > kW2vMaxWindow) throw_error("w2v_oreduce: window must be in [1, 15]");
   const int ntiles = (B + kT - 1) / kT;
@@ -1872,10 +1856,7 @@ void launch_w2v_cbow_keys(uint64_t* keys, long long n, hipStream_t st) {
 // 2: the K <= 16 kernel for every K.  Measured (1M vocab, dim 128, K = 5,
 // serialised): 110.5 / 122.6 / 171 us; step 0.542 / 0.551 / 0.607-0.610 ms
 static int pp_stages() {
-  static const int v = [] {
-    const char* e = std::getenv("SS_W2V_PP_STAGES");
-    return e ? std::atoi(e) : 3;
-  }();
+  static const int v = env_int("SS_W2V_PP_STAGES", 3);
   return v;
 }
 
